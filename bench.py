@@ -7,13 +7,22 @@ graph = the product's launch, Context2Vec.batch_walks): at N = 1 one O2 launch (
 Hogwild, one wavefront per walk); at N > 1 one launch per `--sync-walks` of the rank's walks, each
 followed by the delta all-reduce of both embedding tables over RCCL (overlapped with the next
 launch; the step's last exchange blocking).  The ranks train contiguous shards of ONE corpus
-(weak scaling: per-rank work fixed).  Printed by rank 0: ONE JSON line (contract in the task statement), with
-`roofline` (dominant kernel: achieved algorithmic HBM bytes / launch time vs the 8 TB/s peak) and,
-at N = 1, `cpu_baseline` (the builder's Hogwild C restatement of the reference's CPU path, timed on
-every core this process may use; its ratio to the reference's own Cython is calibrated in the
-container, profiles/r02_cpu_calibration.json).
+(weak scaling: per-rank work fixed).  Printed by rank 0: ONE JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, ...), with
+`roofline` (dominant kernel: achieved algorithmic HBM bytes / launch time vs the 8 TB/s peak,
+from the timed launches' own HIP events).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run does only that: set-up, warm-up, the timed steps, the result line.  `--full` adds what
+takes runs of its own, after the timed region and never part of `value`: at N = 1 `cpu_baseline`
+(the builder's Hogwild C restatement of the reference's CPU path, timed on every core this
+process may use; its ratio to the reference's own Cython was calibrated beside the reference,
+profiles/r02_cpu_calibration.json) and the `secondary` rows (C2 / C4 / walker via bench_aux.py,
+one GPU's share of C5); at N > 1 the C5 row on the job's N GPUs.  `--dump-outputs DIR` writes the
+embedding rows the timed launch's kernel computes as DIR/<name>.npy, reproducibly: the timed
+Hogwild launches race, so the dump repeats the timed call on the head of the last timed step
+with one wavefront in flight, from the untrained tables (dump_outputs).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 """
 import argparse
@@ -89,7 +98,7 @@ def secondary_rows(timeout_s=150):
         if wl == "c5":
             cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--nodes", "10000000",
                    "--dim", "256", "--negative", "10", "--steps", "3", "--warmup", "1",
-                   "--no-secondary", "--cpu-seconds", "6",
+                   "--full", "--no-secondary", "--cpu-seconds", "6",
                    "--traffic-json", os.path.join(ROOT, "profiles", "traffic_c5.json")]
         t0 = time.time()
         try:
@@ -209,6 +218,49 @@ def multi_rank_quality(world, combine, sync_walks, d, n):
     return q
 
 
+DUMP_TABLE_BYTES = 24_000_000  # per table: two tables stay well under 64 MB
+DUMP_WALKS = 1024  # walks of the last timed step that the dump trains
+
+
+def dump_outputs(path, model, learner, init_tables, walks, seeds):
+    """--dump-outputs: float32 `path`/node_embedding.npy and context_embedding.npy, the same in
+    every run with the same arguments, computed by the timed launch's own kernel.
+
+    They are NOT a copy of the tables the timed steps leave.  Those launches are Hogwild: every
+    walk in flight, racing on shared rows as the reference's worker threads do, so their tables
+    differ from run to run far beyond rounding (the same held-out loss, tier C; not the same
+    numbers) and cannot tell two builds apart output for output.  What makes a launch
+    irreproducible is only the number of wavefronts in flight, so the dump repeats the timed call
+    with that number set to one: the timed trainer (`learner`: Hogwild mode, its hot-row bitmap
+    and float atomics, the packed negative table, the device work queue, its launch options;
+    at the benchmark's shapes the same streaming kernel, bench.kernel_name) with the launch
+    option max_waves=1, over the first DUMP_WALKS walks of the last timed step and their seeds,
+    on `init_tables`, copies of the two tables taken before the first step.  One wavefront takes
+    the walks in order, so the result is reproducible bit for bit, and a change to the kernel's
+    arithmetic, its updates or its tails shows in it.  The timed tables are not touched.
+    Written: the rows of the nodes those walks visit, ascending (a RandomState(0) sample of them
+    where they pass DUMP_TABLE_BYTES: 46,875 rows at d = 128)."""
+    import copy
+
+    import torch
+    m = copy.copy(model)
+    m.node_embedding, m.context_embedding = init_tables
+    one = copy.copy(learner)
+    one.distributed = False
+    one.batch_walks = DUMP_WALKS
+    one.launch_opts = dict(learner.launch_opts or {}, max_waves=1)
+    walks, seeds = walks[:DUMP_WALKS].contiguous(), seeds[:DUMP_WALKS].contiguous()
+    one.train_rows(m, walks, seeds, 1.0)
+    rows = torch.unique(walks[walks >= 0]).long()  # sorted
+    keep = DUMP_TABLE_BYTES // (4 * m.node_embedding.shape[1])
+    if rows.numel() > keep:
+        pick = np.sort(np.random.RandomState(0).choice(rows.numel(), keep, replace=False))
+        rows = rows[torch.from_numpy(pick).to(rows.device)]
+    os.makedirs(path, exist_ok=True)
+    for name in ("node_embedding", "context_embedding"):
+        np.save(os.path.join(path, name + ".npy"), getattr(m, name)[rows].float().cpu().numpy())
+
+
 def calibration_ratio():
     try:
         c = json.load(open(os.path.join(ROOT, "profiles", "r02_cpu_calibration.json")))
@@ -268,6 +320,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the CPU "
+                         "baseline and the secondary rows (each can still be switched off with "
+                         "--no-cpu-baseline / --no-secondary); never part of `value`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps repeat the timed launch on the first walks of "
+                         "the last step with one wavefront in flight (reproducible), from the "
+                         "untrained tables, and write the rows they visit as float32 "
+                         "DIR/<name>.npy")
     ap.add_argument("--nodes", type=int, default=1_000_000)
     ap.add_argument("--mean-degree", type=float, default=20.0)  # -> ~10M undirected edges
     ap.add_argument("--dim", type=int, default=128)
@@ -287,10 +348,11 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every CPU this process may use (affinity and cgroup quota)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary rows (N=1: C2 / C4 / walker via bench_aux.py and one "
-                         "GPU's share of C5; N>1: C5 on the job's N GPUs)")
+                    help="with --full: skip the secondary rows (N=1: C2 / C4 / walker via "
+                         "bench_aux.py and one GPU's share of C5; N>1: C5 on the job's N GPUs)")
     ap.add_argument("--c5-nodes", type=int, default=10_000_000,
                     help="N>1: nodes of the C5 secondary row's graph (configs[4]: 10M; smaller "
                          "only to rehearse the multi-process plumbing, e.g. over gloo on one GPU)")
@@ -400,6 +462,10 @@ def main():
                            1.0, update_count=upd_count if count else None,
                            launch_events=events)
 
+    init_tables = None
+    if rank == 0 and args.dump_outputs:  # dump_outputs trains copies of the untrained tables
+        init_tables = (model.node_embedding.clone(), model.context_embedding.clone())
+
     stream = torch.cuda.current_stream(dev)
     for s in range(args.warmup):
         step(s)
@@ -437,8 +503,14 @@ def main():
     assert torch.isfinite(model.node_embedding).all() and torch.isfinite(
         model.context_embedding).all(), "non-finite embedding after training"
 
+    if init_tables is not None:
+        s = total_steps - 1
+        dump_outputs(args.dump_outputs, model, learner, init_tables,
+                     walks_all[s * B:(s + 1) * B], seeds_all[s * B:(s + 1) * B])
+        del init_tables
+
     c5_multi = None
-    if world > 1 and not args.no_secondary:
+    if args.full and world > 1 and not args.no_secondary:
         c5_multi = c5_multi_gpu_row(args, rank, world)
     if rank != 0:
         if world > 1:
@@ -474,7 +546,7 @@ def main():
             traffic = None
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as orc
         sample = min(400_000, walks_all.shape[0])  # more than --cpu-seconds can finish
         wn = walks_all[:sample].cpu().numpy()
@@ -498,7 +570,7 @@ def main():
                              rthreads, "%.3f" % ratio if ratio else "n/a")}
 
     secondary = {"c5": c5_multi} if c5_multi is not None else None
-    if world == 1 and not args.no_secondary:
+    if args.full and world == 1 and not args.no_secondary:
         log("secondary rows (bench_aux.py c2 / c4 / walks, bench.py C5 shard; outside the timed region)")
         secondary = secondary_rows()
 

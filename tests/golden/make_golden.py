@@ -5,11 +5,12 @@ oracle/build_ref.py).  The reference is imported read-only from /root/reference;
 resulting input/output vectors (data) are committed.  Nothing here runs on the GPU box.
 
 Fixtures:
-  kat_o2.npz      per-walk known-answer tests of train_o2 (pyx:454-509), several (d, neg, w, V)
+  kat_o2.N.npz    per-walk known-answer tests of train_o2 (pyx:454-509), several (d, neg, w, V);
+                  in parts (save_parts), like gmm_resp
   kat_o1.npz      per-edge known-answer tests of train_o1 (pyx:407-450)
   make_table.npz  Model.make_table (model.py:97-122) on small degree maps
   community.npz   Community2Vec.train (community_embeddings.py:61-78) on fixed GMM parameters
-  gmm_resp.npz    GaussianMixture.predict_proba + fp32 inv (community_embeddings.py:34-37) for
+  gmm_resp.N.npz  GaussianMixture.predict_proba + fp32 inv (community_embeddings.py:34-37) for
                   fixed (weights, means, covariances)
   karate.npz      the adsc_Karate.py:104-137 flow (workers=1) on the shipped Karate graph, walks
                   generated here with a seeded uniform walker (graph_utils' walker needs
@@ -48,6 +49,28 @@ def load_reference():
     sys.modules["utils.training_sdg_inner"] = mod
     utils.training_sdg_inner = mod
     return mod
+
+
+PART_BYTES = 900 * 1024  # committed files stay under 1 MiB
+
+
+def save_parts(name, out):
+    """Write the arrays of `out` as <name>.0.npz, <name>.1.npz, ...: in order, as many per part as
+    stay under PART_BYTES compressed (tests/conftest.py load_golden merges them again)."""
+    import io
+    parts, size = [{}], 0
+    for k, a in out.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{k: a})
+        n = buf.getbuffer().nbytes
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += n
+    assert len(parts) <= 10
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(HERE, "%s.%d.npz" % (name, i)), **p)
 
 
 class V:  # stands in for utils.embedding.Vocab: the kernels read only .index (pyx:438,488)
@@ -132,7 +155,7 @@ def gen_kat_o2(ref, Model):
                     pre + "margin": np.array(margin)})
         print("kat_o2 %-24s margin=%.3g" % (name, margin))
     out["names"] = np.array([c[0] for c in cases])
-    np.savez_compressed(os.path.join(HERE, "kat_o2.npz"), **out)
+    save_parts("kat_o2", out)
 
 
 def gen_kat_o1(ref, Model):
@@ -269,7 +292,7 @@ def gen_gmm_resp():
                     pre + "pi": pi, pre + "inv32": inv})
         print("gmm_resp %s" % name)
     out["names"] = np.array(["v500_k4_d8", "v300_k6_d128", "v64_k2_d2"])
-    np.savez_compressed(os.path.join(HERE, "gmm_resp.npz"), **out)
+    save_parts("gmm_resp", out)
 
 
 def karate_walks(G, num_paths, length, seed):

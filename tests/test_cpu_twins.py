@@ -14,12 +14,12 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import GOLDEN, load_golden
 from oracle import oracle as orc
 
 cpu = pytest.importorskip("come_amd.cpu")
 
-KAT_O2 = np.load(os.path.join(GOLDEN, "kat_o2.npz"))
+KAT_O2 = load_golden("kat_o2")
 KAT_O1 = np.load(os.path.join(GOLDEN, "kat_o1.npz"))
 
 
@@ -178,7 +178,7 @@ def resp_params(w, mu, pc):
 
 def test_gmm_resp_reference_golden():
     """sklearn predict_proba outputs captured from the reference's GaussianMixture."""
-    z = np.load(os.path.join(GOLDEN, "gmm_resp.npz"))
+    z = load_golden("gmm_resp")
     for name in z["names"]:
         p = name + "_"
         pc = orc.precision_cholesky(z[p + "cov"])

@@ -19,7 +19,7 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import GOLDEN
+from conftest import GOLDEN, load_golden
 from oracle import oracle as orc
 
 import come_amd.training_sdg_inner as tsi
@@ -27,7 +27,7 @@ from come_amd import community_embeddings as ce
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
-KAT_O2 = np.load(os.path.join(GOLDEN, "kat_o2.npz"))
+KAT_O2 = load_golden("kat_o2")
 KAT_O1 = np.load(os.path.join(GOLDEN, "kat_o1.npz"))
 
 
@@ -442,7 +442,7 @@ def test_community_train_node_subset_with_repeats():
 
 
 def test_gmm_resp_vs_golden():
-    z = np.load(os.path.join(GOLDEN, "gmm_resp.npz"))
+    z = load_golden("gmm_resp")
     for name in z["names"]:
         p = name + "_"
         pc = orc.precision_cholesky(z[p + "cov"])

@@ -8,10 +8,10 @@ import os
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import GOLDEN, load_golden
 from oracle import oracle as orc
 
-KAT_O2 = np.load(os.path.join(GOLDEN, "kat_o2.npz"))
+KAT_O2 = load_golden("kat_o2")
 KAT_O1 = np.load(os.path.join(GOLDEN, "kat_o1.npz"))
 
 
@@ -114,7 +114,7 @@ def test_community_golden():
 
 
 def test_gmm_resp_golden():
-    z = np.load(os.path.join(GOLDEN, "gmm_resp.npz"))
+    z = load_golden("gmm_resp")
     for name in z["names"]:
         p = name + "_"
         pi = orc.gmm_predict_proba(z[p + "X"], z[p + "w"], z[p + "mu"], z[p + "cov"])
