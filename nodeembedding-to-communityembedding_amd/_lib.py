@@ -3,6 +3,7 @@
 The HIP library is the only compute path: if it is missing or fails to load, every entry point
 raises -- there is no CPU fallback on the product path.
 """
+import contextlib
 import ctypes
 import os
 
@@ -182,3 +183,17 @@ def launch_opts(update_count=None, **overrides):
     if update_count is not None:
         o.o2_update_count = update_count.data_ptr()
     return o
+
+
+@contextlib.contextmanager
+def options(**kv):
+    """Process-wide launch options set for a `with` block and restored afterwards."""
+    cur = launch_opts()
+    old = {k: getattr(cur, k) for k in kv}
+    try:
+        for k, v in kv.items():
+            set_option(k, v)
+        yield
+    finally:
+        for k, v in old.items():
+            set_option(k, v)

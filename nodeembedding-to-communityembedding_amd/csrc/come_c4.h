@@ -1,13 +1,19 @@
 // come_c4.h -- what the C4 kernels share (gfx950): argument blocks, the bf16-part arithmetic,
-// launch constants and A/B hooks.  Included by come_community.hip (community step),
-// come_gmm_estep.hip (GMM responsibilities) and come_gmm_scatter.hip (M-step scatter matrices).
+// launch constants and the entry points' launch path (launch, with_width).  Included by
+// come_community.hip (community step), come_gmm_estep.hip (GMM responsibilities) and
+// come_gmm_scatter.hip (M-step scatter matrices).  A tuning constant lives in the shape struct
+// that uses it, beside the measurement that chose it; A/B builds go through scripts/build_ab.sh.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <math.h>
+#include <mutex>
+#include <set>
 #include <stdint.h>
+#include <type_traits>
+#include <utility>
 
 #include "come_internal.h"
 #include "come_wave.h"
@@ -15,54 +21,47 @@
 namespace come {
 
 constexpr int kTR = 16;        // rows per workgroup tile
-
-// A/B hook (scripts/build_ab.sh ... -DCOME_AB_PRIO): raise the wave priority over the MFMA
-// clusters of the 16x16x4 kernels (MI355X guide T5); off in the product build.
-#ifdef COME_AB_PRIO
-#define COME_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define COME_PRIO(x) ((void)0)
-#endif
-// A/B hooks of k_gmm_cov16 (build_ab.sh only; results are garbage for DIAG != 0):
-// COME_COV_DIAG 1 = staging re-stages the first 3 blocks' registers (no global loads after the
-// prologue), 2 = MFMA wavefronts consume buffer 0 without barriers (the MFMA stream alone), 3 =
-// every load reads the chunk's first block (the same instructions, cache-resident data).
-// COME_RESP_DIAG (k_gmm_resp16t) 1 = no copies after component 0, 2 = and no barriers (both read
-// the never-written second buffer for odd components: zero-like data, which clocks higher), 3 /
-// 4 = as 1 / 2 with every component read from buffer 0 (real data: component 0 repeated).
-#ifndef COME_COV_DIAG
-#define COME_COV_DIAG 0
-#endif
-#ifndef COME_RESP_DIAG
-#define COME_RESP_DIAG 0
-#endif
-// k_gmm_cov16 at d = 128: staging register sets (3 / 4 / 5+: 7.266 / 7.247 ms at C4 / spills)
-#ifndef COME_COV_NS
-#define COME_COV_NS 4
-#endif
-// k_gmm_cov_bf3 at d = 128: staging wavefronts per workgroup (8: 5.32-5.35 vs 5.49-5.50 ms with 4,
-// profiles/r06_ab_scatter_bf3.txt) and staging register sets (A/B hooks)
-#ifndef COME_COV3_SW
-#define COME_COV3_SW 8
-#endif
-#ifndef COME_COV3_NS
-#define COME_COV3_NS 3
-#endif
-// MFMA wavefronts per d = 128 component (4: 5.50 vs 5.42-5.44 ms with 2, r06zl)
-#ifndef COME_COV3_WPC
-#define COME_COV3_WPC 2
-#endif
-// k_gmm_cov_fb3 (A/B hooks): staging register sets (loads NS blocks ahead; 2: 4.64 vs 4.84 ms with
-// 3 at C4 with SYMU, which at 3 sets needs all 256 VGPRs) and the diagonal tiles' cross terms as
-// U + U^T (0: six MFMAs per diagonal tile as k_gmm_cov_bf3, bit-identical to it; 1: four, 3-5%
-// faster)
-#ifndef COME_COVF_NS
-#define COME_COVF_NS 2
-#endif
-#ifndef COME_COVF_SYMU
-#define COME_COVF_SYMU 1
-#endif
 constexpr int kThreads = 256;
+
+// ---- the entry points' launch path ------------------------------------------------------------
+// Dynamic LDS of a launch and the limit its kernel is allowed (default: the CU's whole 160 KB).
+struct Lds {
+    size_t bytes;
+    int limit = 160 * 1024;
+};
+
+// Raises kern's dynamic-LDS limit the first time it is asked to on `dev` (the entry points are
+// re-entrant: the set of what is done is mutex-guarded).
+inline int raise_lds_limit(int dev, const void *kern, int limit, const char *what) {
+    static std::mutex mu;
+    static std::set<std::pair<const void *, int>> raised;
+    std::lock_guard<std::mutex> lock(mu);
+    if (raised.count({kern, dev})) return COME_OK;
+    const int rc = hip_error(
+        hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, limit), what);
+    if (rc == COME_OK) raised.insert({kern, dev});
+    return rc;
+}
+
+// Launches kern(args...) on `stream` and returns the launch's status (`what` heads the error
+// text).  A kernel launched with dynamic LDS gets its limit raised first (raise_lds_limit).
+template <typename... P, typename... A>
+inline int launch(int dev, void (*kern)(P...), const char *what, dim3 grid, dim3 block, Lds lds,
+                  void *stream, const A &...args) {
+    if (lds.bytes > 0) {
+        const int rc = raise_lds_limit(dev, (const void *)kern, lds.limit, what);
+        if (rc) return rc;
+    }
+    hipLaunchKernelGGL(kern, grid, block, lds.bytes, (hipStream_t)stream, args...);
+    return hip_error(hipGetLastError(), what);
+}
+
+// f(std::integral_constant<int, D>{}) for the MFMA kernels' runtime width d, D in {64, 128}
+template <typename F>
+inline int with_width(int d, F &&f) {
+    if (d == 64) return f(std::integral_constant<int, 64>{});
+    return f(std::integral_constant<int, 128>{});
+}
 
 // out[r][c] = sum_j A[r][j] * B(c, j) for the tile, where B(c, j) = Bm[c*d + j] (TRANS=false,
 // i.e. B used as M @ a) or Bm[j*d + c] (TRANS=true, i.e. a @ B).  A and Bm live in LDS.
@@ -102,8 +101,9 @@ struct RespArgs {
     int d;
     int K;
     const int *lower;  // MFMA path: [K], 1 if prec_chol[k] has a non-zero below the diagonal
-    const float *prec_t;  // MFMA path: [K][d][d] prec_chol[k] transposed (k_transpose_sq)
-    const float *prec_full;  // k_gmm_resp16t: P^T for the FULL body (prec_t = packed blocks)
+    const float *prec_t;  // MFMA path: the upper factors packed (k_pack_upper16 / k_pack_upper_b16)
+    const float *prec_full;  // MFMA path: [K][d][d] prec_chol[k] transposed (k_transpose_sq), which
+                             // k_gmm_resp16_full reads
 };
 
 // ---- fp32 operands as bf16 parts: the arithmetic of the C4 default kernels --------------------

@@ -153,7 +153,6 @@ __device__ __forceinline__ void comm16_phase(const __attribute__((ext_vector_typ
     f32x4 av[3];
     av[0] = fetch(0);
     av[1] = fetch(1);
-    COME_PRIO(1);
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
         if (n + 2 < NB) av[(n + 2) % 3] = fetch(n + 2);
@@ -163,7 +162,6 @@ __device__ __forceinline__ void comm16_phase(const __attribute__((ext_vector_typ
             acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[n % 3][t], bq[qq][t], acc[ct], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
-    COME_PRIO(0);
 }
 
 template <int D>
@@ -476,69 +474,35 @@ extern "C" int come_community_grad(float *x, int64_t V, int d, const float *pi, 
     const int variant = current_opts().community_async;
     if (variant != 2 && variant != 3)
         return set_error(COME_E_INVALID, "community_async must be 2 or 3 (got %d)", variant);
-    if ((d == 64 || d == 128) && ((uintptr_t)inv_cov % 16) == 0 && ((uintptr_t)mu % 16) == 0 &&
-        variant == 3) {
-        // k_comm_split16 (the bf16 part images of every inv_cov[k], once per call) + k_community_b16
-        const size_t ub = d == 64 ? CommB16<64>::UBYTES : CommB16<128>::UBYTES;
-        char *img = (char *)stream_scratch(dev, stream, kScratchCommSplit, (size_t)K * (d / 32) * ub);
-        if (!img) return scratch_failed();
-        const int64_t work = (int64_t)K * (d / 32) * d * 4;
-        hipLaunchKernelGGL(d == 64 ? k_comm_split16<64> : k_comm_split16<128>,
-                           dim3((unsigned)std::min<int64_t>((work + 255) / 256, 4096)), dim3(256), 0,
-                           (hipStream_t)stream, inv_cov, img, K);
-        rc = hip_error(hipGetLastError(), "k_comm_split16 launch");
-        if (rc) return rc;
-        a.img = img;
-        static bool attr3 = false;
-        if (!attr3) {
-            for (void (*f)(CommArgs) : {k_community_b16<64>, k_community_b16<128>})
-                (void)hipFuncSetAttribute((const void *)f,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr3 = true;
-        }
-        hipLaunchKernelGGL(d == 64 ? k_community_b16<64> : k_community_b16<128>,
-                           dim3((unsigned)((V + 127) / 128)), dim3(512),
-                           d == 64 ? CommB16<64>::LDS_BYTES : CommB16<128>::LDS_BYTES,
-                           (hipStream_t)stream, a);
-        return hip_error(hipGetLastError(), "k_community_b16 launch");
-    }
-    if ((d == 64 || d == 128) && ((uintptr_t)inv_cov % 16) == 0 && ((uintptr_t)mu % 16) == 0) {
-        // 2: the fp32 form k_community16
-        void (*kern)(CommArgs) = d == 64 ? k_community16<64> : k_community16<128>;
-        const size_t lds =
-            sizeof(float) * (size_t)(d == 64 ? Comm16<64>::LDS_FLOATS : Comm16<128>::LDS_FLOATS);
-        static bool attr = false;
-        if (!attr) {
-            for (void (*f)(CommArgs) : {k_community16<64>, k_community16<128>})
-                (void)hipFuncSetAttribute((const void *)f,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr = true;
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)((V + 127) / 128)), dim3(512), lds,
-                           (hipStream_t)stream, a);
-        return hip_error(hipGetLastError(), "community MFMA launch");
-    }
+    const dim3 rows128((unsigned)((V + 127) / 128));
+    if ((d == 64 || d == 128) && ((uintptr_t)inv_cov % 16) == 0 && ((uintptr_t)mu % 16) == 0)
+        return with_width(d, [&](auto width) {
+            constexpr int D = decltype(width)::value;
+            if (variant == 2)  // the fp32 form k_community16
+                return launch(dev, k_community16<D>, "community MFMA launch", rows128, dim3(512),
+                              {sizeof(float) * Comm16<D>::LDS_FLOATS}, stream, a);
+            // k_comm_split16 (the bf16 part images of every inv_cov[k], once per call), then
+            // k_community_b16
+            using C = CommB16<D>;
+            char *img = (char *)stream_scratch(dev, stream, kScratchCommSplit,
+                                               (size_t)K * C::NS * C::UBYTES);
+            if (!img) return scratch_failed();
+            const int64_t work = (int64_t)K * C::NS * D * 4;
+            const int rc = launch(dev, k_comm_split16<D>, "k_comm_split16 launch",
+                                  dim3((unsigned)std::min<int64_t>((work + 255) / 256, 4096)),
+                                  dim3(256), {0}, stream, inv_cov, img, K);
+            if (rc) return rc;
+            a.img = img;
+            return launch(dev, k_community_b16<D>, "k_community_b16 launch", rows128, dim3(512),
+                          {C::LDS_BYTES}, stream, a);
+        });
     if (d > 128) {
-        const size_t lds = sizeof(float) * ((size_t)3 * kTRW * d +
-                                            (size_t)chunk_rows(d) * (d + 1) + kTRW);
-        static bool attr_w = false;
-        if (!attr_w) {
-            (void)hipFuncSetAttribute((const void *)k_community_grad_wide,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_w = true;
-        }
-        hipLaunchKernelGGL(k_community_grad_wide, dim3((unsigned)((V + kTRW - 1) / kTRW)),
-                           dim3(kThreads), lds, (hipStream_t)stream, a);
-        return hip_error(hipGetLastError(), "k_community_grad_wide launch");
+        const size_t floats = (size_t)3 * kTRW * d + (size_t)chunk_rows(d) * (d + 1) + kTRW;
+        return launch(dev, k_community_grad_wide, "k_community_grad_wide launch",
+                      dim3((unsigned)((V + kTRW - 1) / kTRW)), dim3(kThreads),
+                      {sizeof(float) * floats}, stream, a);
     }
-    const size_t lds = sizeof(float) * ((size_t)3 * kTR * d + (size_t)d * d);
-    const unsigned grid = (unsigned)((V + kTR - 1) / kTR);
-    static bool attr_v = false;
-    if (!attr_v) {
-        (void)hipFuncSetAttribute((const void *)k_community_grad,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_v = true;
-    }
-    hipLaunchKernelGGL(k_community_grad, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-    return hip_error(hipGetLastError(), "k_community_grad launch");
+    return launch(dev, k_community_grad, "k_community_grad launch",
+                  dim3((unsigned)((V + kTR - 1) / kTR)), dim3(kThreads),
+                  {sizeof(float) * ((size_t)3 * kTR * d + (size_t)d * d)}, stream, a);
 }

@@ -457,7 +457,6 @@ __device__ __forceinline__ void r16t_blocks(
     f32x4 av[3];
     av[0] = fetch(0);
     av[1] = fetch(1);
-    COME_PRIO(1);
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
         if (n + 2 < NB) av[(n + 2) % 3] = fetch(n + 2);
@@ -470,7 +469,6 @@ __device__ __forceinline__ void r16t_blocks(
             acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[n % 3][t], xb[q][t], acc[ct], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
-    COME_PRIO(0);
 }
 
 // the epilogue of one component: sq += |acc[ct] - (mu_k P_k)[ct]|^2 over the column tiles ct in
@@ -553,24 +551,23 @@ __global__ void __launch_bounds__(R16tShape::THREADS, R16tShape::WPE) k_gmm_resp
     const bool owner = kg == 0 && my_row < a.V;
     float run_max = -INFINITY, run_sum = 0.0f, lp_prev = 0.0f;
     for (int k = 0; k < a.K; ++k) {
-        const int kb = COME_RESP_DIAG >= 3 ? 0 : k;  // the buffer read
         // component k - 1's log-probability is stored one component late: a store counts on the
         // vector-memory counter like the staging copies, so storing it right before the barrier's
         // vmcnt(0) made every wavefront wait out the store's round trip once per component
         if (k > 0 && owner) a.resp[my_row * a.K + k - 1] = lp_prev;
-        const float *par = T::slot(sm, kb);
+        const float *par = T::slot(sm, k);
         f32x4 acc[NQ];
         // component k + 1's copy (4-5 1-KiB LDS-DMA pieces per wavefront at d = 128) issued one
         // piece every SP blocks from block 3 instead of all at the component's head, where they sat
         // on the MFMA ramp: 6.95 vs 7.01 ms at C4 (SP = 7) (spacing 2 / 4 / 8 / 6 from block 4: 7.01 / 6.99 / 6.99 /
         // 6.95; profiles/r05_ab_gmm_diag.txt)
-        r16t_blocks<D>(xb, T::blocks(sm, kb), abase, acc, [&](int n) {
+        r16t_blocks<D>(xb, T::blocks(sm, k), abase, acc, [&](int n) {
             constexpr int NB = T::NQ * (T::NQ + 1) / 2, OFF = 3;
             constexpr int PER = (T::PIECES + R16tShape::NW - 1) / R16tShape::NW;
             constexpr int SP = (NB - OFF + PER - 1) / PER;  // 7 at d = 128, 4 at d = 64
             static_assert(OFF + SP * (PER - 1) < NB, "every piece lands on a block");
             const int m = n - OFF;
-            if (!COME_RESP_DIAG && m >= 0 && m % SP == 0 && m / SP < PER && k + 1 < a.K)
+            if (m >= 0 && m % SP == 0 && m / SP < PER && k + 1 < a.K)
                 r16t_stage_piece<D>(a, k + 1, T::blocks(sm, k + 1), T::slot(sm, k + 1), wid, lane,
                                     m / SP);
         });
@@ -580,10 +577,8 @@ __global__ void __launch_bounds__(R16tShape::THREADS, R16tShape::WPE) k_gmm_resp
         const float lp = r16t_lp_of<D>(sq, par);
         lse_push(lp, run_max, run_sum);
         lp_prev = lp;
-#if COME_RESP_DIAG != 2 && COME_RESP_DIAG != 4
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // buffer k & 1 free; component k + 1 in the other buffer
-#endif
     }
     if (owner) {
         float *lp = a.resp + my_row * a.K;
@@ -865,122 +860,77 @@ extern "C" int come_gmm_estep(const float *x, int64_t V, int d, const float *pre
     if (rc) return rc;
     RespArgs a{x, prec_chol, mu_prec, log_norm, resp_out, lse_out, V, d, K, nullptr};
     if (mfma) {
+        const int r16 = current_opts().gmm_resp16;
+        if (r16 != 2 && r16 != 3)
+            return set_error(COME_E_INVALID, "gmm_resp16 must be 2 or 3 (got %d)", r16);
         int *flags = (int *)stream_scratch(dev, stream, kScratchGmmFlags, sizeof(int) * (K + 1));
         if (!flags) return scratch_failed();
         rc = hip_error(hipMemsetAsync(flags + K, 0, sizeof(int), (hipStream_t)stream),
                        "gmm_resp: flag reset");
         if (rc) return rc;
-        hipLaunchKernelGGL(k_gmm_lower_flags, dim3(K), dim3(256), 0, (hipStream_t)stream,
-                           prec_chol, d, flags, K);
-        rc = hip_error(hipGetLastError(), "k_gmm_lower_flags launch");
+        rc = launch(dev, k_gmm_lower_flags, "k_gmm_lower_flags launch", dim3(K), dim3(256), {0},
+                    stream, prec_chol, d, flags, K);
         if (rc) return rc;
         a.lower = flags;
         float *pt = stream_scratch(dev, stream, kScratchGmmPt, sizeof(float) * (size_t)K * d * d);
         if (!pt) return scratch_failed();
-        hipLaunchKernelGGL(k_transpose_sq, dim3((d / 32) * (d / 32), K), dim3(256), 0,
-                           (hipStream_t)stream, prec_chol, d, pt);
-        rc = hip_error(hipGetLastError(), "k_transpose_sq launch");
+        rc = launch(dev, k_transpose_sq, "k_transpose_sq launch", dim3((d / 32) * (d / 32), K),
+                    dim3(256), {0}, stream, prec_chol, d, pt);
         if (rc) return rc;
-        a.prec_t = pt;
-        const int r16 = current_opts().gmm_resp16;
-        if (r16 == 3) {
-            // default: k_gmm_resp_b16 over the bf16-part images of the upper factors, then
-            // k_gmm_resp16_full (a no-op unless some factor is lower or dense)
-            const size_t img_bytes =
-                (size_t)K * (d == 64 ? RespB16<64>::NB : RespB16<128>::NB) * RespB16<64>::BLK;
-            char *img = (char *)stream_scratch(dev, stream, kScratchRespSplit, img_bytes);
-            if (!img) return scratch_failed();
-            const int64_t work = (int64_t)K * (d == 64 ? RespB16<64>::NB : RespB16<128>::NB) * 64;
-            hipLaunchKernelGGL(d == 64 ? k_pack_upper_b16<64> : k_pack_upper_b16<128>,
-                               dim3((unsigned)std::min<int64_t>((work + 255) / 256, 4096)),
-                               dim3(256), 0, (hipStream_t)stream, prec_chol, img, K);
-            rc = hip_error(hipGetLastError(), "k_pack_upper_b16 launch");
-            if (rc) return rc;
-            RespArgs b = a;
-            b.prec_full = a.prec_t;
-            b.prec_t = reinterpret_cast<const float *>(img);
-            static bool attr3 = false;
-            if (!attr3) {
-                for (void (*f)(RespArgs) : {k_gmm_resp_b16<64>, k_gmm_resp_b16<128>,
-                                            k_gmm_resp16_full<64>, k_gmm_resp16_full<128>})
-                    (void)hipFuncSetAttribute((const void *)f,
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr3 = true;
+        a.prec_full = pt;
+        // The upper factors packed for the main kernel (a no-op if some factor is lower or dense),
+        // then k_gmm_resp16_full (a no-op unless one is).  3 (default): k_gmm_resp_b16 over the
+        // bf16-part images; 2: k_gmm_resp16t over the non-zero fp32 blocks.
+        return with_width(d, [&](auto width) {
+            constexpr int D = decltype(width)::value;
+            void (*kern)(RespArgs);
+            const char *what;
+            dim3 grid, block;
+            Lds lds;
+            int rc;
+            if (r16 == 3) {
+                using R = RespB16<D>;
+                char *img = (char *)stream_scratch(dev, stream, kScratchRespSplit,
+                                                   (size_t)K * R::NB * R::BLK);
+                if (!img) return scratch_failed();
+                const int64_t work = (int64_t)K * R::NB * 64;
+                rc = launch(dev, k_pack_upper_b16<D>, "k_pack_upper_b16 launch",
+                            dim3((unsigned)std::min<int64_t>((work + 255) / 256, 4096)), dim3(256),
+                            {0}, stream, prec_chol, img, K);
+                a.prec_t = reinterpret_cast<const float *>(img);
+                kern = k_gmm_resp_b16<D>, what = "k_gmm_resp_b16 launch";
+                grid = dim3((unsigned)((V + 127) / 128)), block = dim3(512);
+                lds = {R::LDS_BYTES};
+            } else {
+                using T = Resp16T<D>;
+                float *packed = stream_scratch(dev, stream, kScratchGmmTri,
+                                               sizeof(float) * (size_t)K * T::TRI);
+                if (!packed) return scratch_failed();
+                rc = launch(dev, k_pack_upper16<D>, "k_pack_upper16 launch",
+                            dim3((unsigned)((T::TRI + 255) / 256), K), dim3(256), {0}, stream,
+                            prec_chol, packed);
+                a.prec_t = packed;
+                kern = k_gmm_resp16t<D>, what = "k_gmm_resp16t launch";
+                grid = dim3((unsigned)((V + R16tShape::ROWS - 1) / R16tShape::ROWS));
+                block = dim3(R16tShape::THREADS);
+                lds = {sizeof(float) * T::LDS};
             }
-            hipLaunchKernelGGL(d == 64 ? k_gmm_resp_b16<64> : k_gmm_resp_b16<128>,
-                               dim3((unsigned)((V + 127) / 128)), dim3(512),
-                               d == 64 ? RespB16<64>::LDS_BYTES : RespB16<128>::LDS_BYTES,
-                               (hipStream_t)stream, b);
-            rc = hip_error(hipGetLastError(), "k_gmm_resp_b16 launch");
             if (rc) return rc;
-            const size_t lds16 = sizeof(float) * (size_t)(d == 64 ? Resp16Shape<64>::LDS
-                                                                   : Resp16Shape<128>::LDS);
-            const int64_t blks = (V + 127) / 128;
-            hipLaunchKernelGGL(d == 64 ? k_gmm_resp16_full<64> : k_gmm_resp16_full<128>,
-                               dim3((unsigned)std::min<int64_t>(blks, 2 * (int64_t)num_cus(dev))),
-                               dim3(256), lds16, (hipStream_t)stream, b);
-            return hip_error(hipGetLastError(), "k_gmm_resp16_full launch");
-        }
-        if (r16 == 2) {
-            // default: k_gmm_resp16t over the packed non-zero blocks (every factor upper-
-            // triangular), then k_gmm_resp16_full (a no-op unless some factor is lower or dense)
-            const int tri = d == 64 ? Resp16T<64>::TRI : Resp16T<128>::TRI;
-            float *packed = stream_scratch(dev, stream, kScratchGmmTri, sizeof(float) * (size_t)K * tri);
-            if (!packed) return scratch_failed();
-            hipLaunchKernelGGL(d == 64 ? k_pack_upper16<64> : k_pack_upper16<128>,
-                               dim3((unsigned)((tri + 255) / 256), K), dim3(256), 0,
-                               (hipStream_t)stream, prec_chol, packed);
-            rc = hip_error(hipGetLastError(), "k_pack_upper16 launch");
-            if (rc) return rc;
-            RespArgs b = a;
-            b.prec_full = a.prec_t;
-            b.prec_t = packed;
-            const size_t ldst = sizeof(float) * (size_t)(d == 64 ? Resp16T<64>::LDS : Resp16T<128>::LDS);
-            const size_t lds16 = sizeof(float) * (size_t)(d == 64 ? Resp16Shape<64>::LDS
-                                                                   : Resp16Shape<128>::LDS);
-            static bool attr16t = false;
-            if (!attr16t) {
-                for (void (*f)(RespArgs) : {k_gmm_resp16t<64>, k_gmm_resp16t<128>,
-                                            k_gmm_resp16_full<64>, k_gmm_resp16_full<128>})
-                    (void)hipFuncSetAttribute((const void *)f,
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr16t = true;
-            }
-            hipLaunchKernelGGL(d == 64 ? k_gmm_resp16t<64> : k_gmm_resp16t<128>,
-                               dim3((unsigned)((V + R16tShape::ROWS - 1) / R16tShape::ROWS)),
-                               dim3(R16tShape::THREADS), ldst,
-                               (hipStream_t)stream, b);
-            rc = hip_error(hipGetLastError(), "k_gmm_resp16t launch");
+            rc = launch(dev, kern, what, grid, block, lds, stream, a);
             if (rc) return rc;
             const int64_t blks = (V + 127) / 128;
-            hipLaunchKernelGGL(d == 64 ? k_gmm_resp16_full<64> : k_gmm_resp16_full<128>,
-                               dim3((unsigned)std::min<int64_t>(blks, 2 * (int64_t)num_cus(dev))),
-                               dim3(256), lds16, (hipStream_t)stream, b);
-            return hip_error(hipGetLastError(), "k_gmm_resp16_full launch");
-        }
-        return set_error(COME_E_INVALID, "gmm_resp16 must be 2 or 3 (got %d)", r16);
+            return launch(dev, k_gmm_resp16_full<D>, "k_gmm_resp16_full launch",
+                          dim3((unsigned)std::min<int64_t>(blks, 2 * (int64_t)num_cus(dev))),
+                          dim3(256), {sizeof(float) * Resp16Shape<D>::LDS}, stream, a);
+        });
     }
     if (d > 128) {
-        const size_t lds = sizeof(float) * ((size_t)2 * kTRW * d +
-                                            (size_t)chunk_rows(d) * (d + 1) + kTRW);
-        static bool attr_w = false;
-        if (!attr_w) {
-            (void)hipFuncSetAttribute((const void *)k_gmm_resp_wide,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_w = true;
-        }
-        hipLaunchKernelGGL(k_gmm_resp_wide, dim3((unsigned)((V + kTRW - 1) / kTRW)),
-                           dim3(kThreads), lds, (hipStream_t)stream, a);
-        return hip_error(hipGetLastError(), "k_gmm_resp_wide launch");
+        const size_t floats = (size_t)2 * kTRW * d + (size_t)chunk_rows(d) * (d + 1) + kTRW;
+        return launch(dev, k_gmm_resp_wide, "k_gmm_resp_wide launch",
+                      dim3((unsigned)((V + kTRW - 1) / kTRW)), dim3(kThreads),
+                      {sizeof(float) * floats}, stream, a);
     }
-    const size_t lds = sizeof(float) * ((size_t)kTR * d + (size_t)d * d + kTR * 64 + kTR);
-    const unsigned grid = (unsigned)((V + kTR - 1) / kTR);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void *)k_gmm_resp,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
-    hipLaunchKernelGGL(k_gmm_resp, dim3(grid), dim3(kThreads), lds, (hipStream_t)stream, a);
-    return hip_error(hipGetLastError(), "k_gmm_resp launch");
+    return launch(dev, k_gmm_resp, "k_gmm_resp launch", dim3((unsigned)((V + kTR - 1) / kTR)),
+                  dim3(kThreads),
+                  {sizeof(float) * ((size_t)kTR * d + (size_t)d * d + kTR * 64 + kTR)}, stream, a);
 }

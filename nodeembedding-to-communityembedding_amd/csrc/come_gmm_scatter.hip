@@ -103,18 +103,9 @@ __device__ __forceinline__ void cov16_consume(const float *img, int nb, int tk, 
     using f32x4 = __attribute__((ext_vector_type(4))) float;
     constexpr Cov16Tiles<D> TT{};
     const int j16 = lane & 15, kg = lane >> 4;
-#if COME_COV_DIAG == 2
-    __syncthreads();
-#endif
     for (int j = 0; j < nb; ++j) {
-#if COME_COV_DIAG == 2
-        asm volatile("" ::: "memory");  // keep the LDS reads in the loop
-        const float *buf = img;
-#else
         __syncthreads();  // barrier j: block j staged
         const float *buf = img + (j % C::NBUF) * C::BUF;
-#endif
-        COME_PRIO(1);
         const float *im = buf + tk * C::IMG;
 #pragma unroll
         for (int g = 0; g < C::RB / 16; ++g) {
@@ -141,7 +132,6 @@ __device__ __forceinline__ void cov16_consume(const float *img, int nb, int tk, 
                 if (n + 1 < C::NTW && TT.ct[P][n + 1] != TT.ct[P][n]) cur ^= 1;
             }
         }
-        COME_PRIO(0);
     }
 }
 
@@ -193,7 +183,8 @@ struct Cov16StageX4 {
     const int sg, fq, wk, ws, k0, nk;
     const bool xl, wlane;
     const int64_t c0, c1;
-    static constexpr int NS = COME_COV_NS;  // register sets: loads run NS blocks ahead
+    // register sets: loads run NS blocks ahead (3 / 4 / 5+: 7.266 / 7.247 ms at C4 / spills)
+    static constexpr int NS = 4;
     float mu[CPW][4];
     f32x4 xv[NS][4];
     float wl[NS];
@@ -212,7 +203,7 @@ struct Cov16StageX4 {
     // leaves the compiler unable to count the loads in flight, and it then waits for all of them
     // (vmcnt(0)) before every stage -- the three-block lookahead collapses to none.
     __device__ __forceinline__ void load(int u, int blk) {
-        const int64_t b = c0 + (COME_COV_DIAG == 3 ? 0 : (int64_t)blk * RB);
+        const int64_t b = c0 + (int64_t)blk * RB;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int64_t r = min(b + 4 * sg + t, c1 - 1);
@@ -223,7 +214,7 @@ struct Cov16StageX4 {
     }
     __device__ __forceinline__ void stage(float *img, int u, int blk) const {
         float *buf = img + (blk % C::NBUF) * C::BUF;
-        const int64_t b = c0 + (COME_COV_DIAG == 3 ? 0 : (int64_t)blk * RB);
+        const int64_t b = c0 + (int64_t)blk * RB;
         // (the values are read outside any branch: a register read under a divergent branch
         // also makes the compiler drain every load in flight)
         const float w = wk < nk && b + ws < c1 ? wl[u] : 0.0f;
@@ -270,7 +261,7 @@ struct Cov16StageCol {
     }
     // unconditional loads, out-of-range values zeroed when staged (as Cov16StageX4)
     __device__ __forceinline__ void load(int u, int blk) {
-        const int64_t b = c0 + (COME_COV_DIAG == 3 ? 0 : (int64_t)blk * RB);
+        const int64_t b = c0 + (int64_t)blk * RB;
 #pragma unroll
         for (int q = 0; q < SPT; ++q) xv[u][q] = a.x[min(b + SPT * sp + q, c1 - 1) * D + sc];
         const int64_t wrow = min(b + SPT * sp + ws, c1 - 1);
@@ -278,7 +269,7 @@ struct Cov16StageCol {
     }
     __device__ __forceinline__ void stage(float *img, int u, int blk) const {
         float *buf = img + (blk % C::NBUF) * C::BUF;
-        const int64_t b = c0 + (COME_COV_DIAG == 3 ? 0 : (int64_t)blk * RB);
+        const int64_t b = c0 + (int64_t)blk * RB;
 #pragma unroll
         for (int kk = 0; kk < CPW; ++kk)
 #pragma unroll
@@ -308,13 +299,8 @@ __device__ __forceinline__ void cov16_staging(float *img, S &sg, int nb) {
     const int last = nb - 1;
 #pragma unroll
     for (int u = 0; u < NS; ++u) sg.load(u, min(u, last));
-#if COME_COV_DIAG == 2
     sg.stage(img, 0, 0);
-    __syncthreads();
-    return;
-#endif
-    sg.stage(img, 0, 0);
-    if (COME_COV_DIAG != 1) sg.load(0, min(NS, last));
+    sg.load(0, min(NS, last));
     __syncthreads();  // barrier 0
     for (int j0 = 0; j0 < nb; j0 += NS) {
 #pragma unroll
@@ -322,7 +308,7 @@ __device__ __forceinline__ void cov16_staging(float *img, S &sg, int nb) {
             const int j = j0 + u;
             if (j >= nb) return;  // (not break: the loop head then sees one load order only)
             sg.stage(img, (u + SD) % NS, j + SD);
-            if (COME_COV_DIAG != 1) sg.load((u + SD) % NS, min(j + SD + NS, last));
+            sg.load((u + SD) % NS, min(j + SD + NS, last));
             if (j + 1 < nb) __syncthreads();  // barrier j + 1
         }
     }
@@ -380,9 +366,12 @@ template <int D>
 struct CovBf3 {
     static constexpr int RB = 32;                   // samples per block (2 k-steps)
     static constexpr int CPW = D == 128 ? 2 : 4;    // components per workgroup
-    static constexpr int WPC = D == 128 ? COME_COV3_WPC : 1;  // MFMA wavefronts per component
+    // MFMA wavefronts per component (d = 128, 4: 5.50 vs 5.42-5.44 ms with 2)
+    static constexpr int WPC = D == 128 ? 2 : 1;
     static constexpr int AW = CPW * WPC;            // MFMA wavefronts (4)
-    static constexpr int SW = D == 128 ? COME_COV3_SW : 4;  // staging wavefronts
+    // staging wavefronts (d = 128, 8: 5.32-5.35 vs 5.49-5.50 ms with 4,
+    // profiles/r06_ab_scatter_bf3.txt)
+    static constexpr int SW = D == 128 ? 8 : 4;
     static constexpr int THREADS = 64 * (AW + SW);
     static constexpr int NF = D / 32;               // fragments (32-feature row groups)
     static constexpr int PLANE = D * RB * 2;        // bytes per part image (D rows x 32 bf16)
@@ -405,30 +394,21 @@ struct CovBf3 {
 // tile n of MFMA part p: (row group ta, column group tb), ta <= tb
 template <int D>
 struct CovBf3Tiles {
-    static constexpr int WPC = CovBf3<D>::WPC;
-    int cnt[4], ta[4][5], tb[4][5];
-    bool need[4][4];  // fragments a part reads
+    int cnt[2], ta[2][5], tb[2][5];
+    bool need[2][4];  // fragments a part reads
     constexpr CovBf3Tiles() : cnt(), ta(), tb(), need() {
-        // d = 128: 10 upper tiles per component, 5 / 5 over 2 wavefronts or 3 / 3 / 2 / 2 over 4
+        // d = 128: 10 upper tiles per component, 5 / 5 over 2 wavefronts
         const int a2[2][5] = {{0, 0, 0, 0, 3}, {1, 1, 1, 2, 2}};
         const int b2[2][5] = {{0, 1, 2, 3, 3}, {1, 2, 3, 2, 3}};
-        const int a4[4][3] = {{0, 0, 0}, {0, 1, 3}, {1, 1, 0}, {2, 2, 0}};
-        const int b4[4][3] = {{0, 1, 2}, {3, 3, 3}, {1, 2, 0}, {2, 3, 0}};
-        const int c4[4] = {3, 3, 2, 2};
-        for (int p = 0; p < 4; ++p) {
-            if (D == 128 && WPC == 2 && p < 2) {
+        static_assert(CovBf3<D>::WPC == (D == 128 ? 2 : 1), "one part per MFMA wavefront");
+        for (int p = 0; p < 2; ++p) {
+            if (D == 128) {
                 cnt[p] = 5;
                 for (int n = 0; n < 5; ++n) {
                     ta[p][n] = a2[p][n];
                     tb[p][n] = b2[p][n];
                 }
-            } else if (D == 128 && WPC == 4) {
-                cnt[p] = c4[p];
-                for (int n = 0; n < c4[p]; ++n) {
-                    ta[p][n] = a4[p][n];
-                    tb[p][n] = b4[p][n];
-                }
-            } else if (D == 64 && p == 0) {
+            } else if (p == 0) {
                 const int a0[3] = {0, 0, 1}, b0[3] = {0, 1, 1};
                 cnt[p] = 3;
                 for (int n = 0; n < 3; ++n) {
@@ -510,7 +490,7 @@ template <int D>
 struct CovBf3Stage {
     using C = CovBf3<D>;
     static constexpr int SPT = C::SPT, CPW = C::CPW;
-    static constexpr int NS = COME_COV3_NS;  // register sets: loads run NS blocks ahead
+    static constexpr int NS = 3;  // register sets: loads run NS blocks ahead
     const CovArgs &a;
     const int f, sg, k0, nk, lane;
     const int64_t c0, c1;
@@ -584,14 +564,9 @@ __global__ void __launch_bounds__(CovBf3<D>::THREADS) __attribute__((amdgpu_wave
     const int nb = c1 > c0 ? (int)((c1 - c0 + C::RB - 1) / C::RB) : 0;
     const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     if (wid < C::AW) {
-        // wavefronts w and w + 4 share a SIMD: with 4 parts per component, component 1's part
-        // index is shifted by 2 so that each SIMD gets 3 + 2 tiles
-        const int tk = wid / C::WPC;
-        const int p = C::WPC == 4 ? (wid % 4 + 2 * tk) % 4 : wid % C::WPC;
+        const int tk = wid / C::WPC, p = wid % C::WPC;
         if (p == 0) covbf3_part<D, 0>(a, smb, nb, tk, nk, k0, chunk, lane);
-        else if (p == 1) covbf3_part<D, (C::WPC > 1 ? 1 : 0)>(a, smb, nb, tk, nk, k0, chunk, lane);
-        else if (p == 2) covbf3_part<D, (C::WPC > 2 ? 2 : 0)>(a, smb, nb, tk, nk, k0, chunk, lane);
-        else covbf3_part<D, (C::WPC > 2 ? 3 : 0)>(a, smb, nb, tk, nk, k0, chunk, lane);
+        else covbf3_part<D, C::WPC - 1>(a, smb, nb, tk, nk, k0, chunk, lane);
         return;
     }
     // cov16_staging's look-ahead is Cov16<D>::NBUF - 1 blocks, while CovBf3Stage::stage and
@@ -615,7 +590,7 @@ __global__ void __launch_bounds__(CovBf3<D>::THREADS) __attribute__((amdgpu_wave
 // 16-feature block transposed: lane i gets feature i of the 4 samples), so a staging lane's weight
 // is its own sample's (no broadcast) and its x is two 16-byte loads.  Diagonal tiles take their
 // cross terms a1 b2 + a2 b1 + a1 b3 + a3 b1 as U + U^T, U = a1 b2 + a1 b3: four MFMAs instead of six,
-// U^T added once at the end (COME_COVF_SYMU).
+// U^T added once at the end (3-5% faster than k_gmm_cov_bf3's six, whose bits it then leaves).
 template <int D>
 struct CovFb3 {
     static_assert(D == 128, "k_gmm_cov_fb3 covers d = 128 (k_gmm_cov_bf3 takes d = 64)");
@@ -627,7 +602,9 @@ struct CovFb3 {
     static constexpr int IMG = 3 * PLANE;        // per component
     static constexpr int BUF = CPW * IMG;        // 24 KB
     static constexpr int LDS_BYTES = 2 * BUF;    // 48 KB
-    static constexpr int NS = COME_COVF_NS;      // staging register sets (loads NS blocks ahead)
+    // staging register sets (loads NS blocks ahead; 2: 4.64 vs 4.84 ms with 3 at C4, which needs
+    // all 256 VGPRs)
+    static constexpr int NS = 2;
     // chunk ch (16 B, 8 features) of sample row r of part P: chunks XOR-swizzled by the row, so each
     // tr read's 32-lane half (4 rows x 4 chunks x two 8-B halves: 256 B) and each 8-lane
     // ds_write_b128 group (8 chunks of one row: 128 B) cover distinct banks
@@ -705,7 +682,7 @@ __device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, int nb,
     for (int n = 0; n < NT; ++n)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[n][e] = 0.0f;
-    constexpr int NDG = COME_COVF_SYMU ? 2 : 1;
+    constexpr int NDG = 2;  // diagonal tiles per part
     f32x16 accu[NDG];
 #pragma unroll
     for (int n = 0; n < NDG; ++n)
@@ -739,7 +716,7 @@ __device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, int nb,
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             const int ta = TT.ta[P][n], tb = TT.tb[P][n];
-            if (COME_COVF_SYMU && ta == tb) {
+            if (ta == tb) {
                 const int dg = TT.dslot(P, n);
                 accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][2], accu[dg], 0, 0, 0);
                 accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][1], accu[dg], 0, 0, 0);
@@ -775,7 +752,6 @@ __device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, int nb,
         }
     }
     if (tk >= nk) return;  // wavefront-uniform: K not a multiple of CPW
-#if COME_COVF_SYMU
     if (nb > 0) {
         float *ut = reinterpret_cast<float *>(smb) + wid * (NDG * 32 * 33);
 #pragma unroll
@@ -790,7 +766,6 @@ __device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, int nb,
                 acc[n][r] += accu[dg][r] + u[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h];
         }
     }
-#endif
     float *out = a.out + (chunk * a.K + k0 + tk) * D * D;
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
@@ -981,29 +956,20 @@ __global__ void __launch_bounds__(256) k_gmm_cov_reduce_upper(const float *part,
     }
 }
 
-static int launch_cov_reduce(const float *part, float *out, int64_t n, int chunks,
-                             hipStream_t stream) {
-    const unsigned grid = (unsigned)((n + 1023) / 1024);
-    if (n % 4 == 0)
-        hipLaunchKernelGGL(k_gmm_cov_reduce<true>, dim3(grid), dim3(256), 0, stream, part, out, n,
-                           chunks);
-    else
-        hipLaunchKernelGGL(k_gmm_cov_reduce<false>, dim3(grid), dim3(256), 0, stream, part, out, n,
-                           chunks);
-    return hip_error(hipGetLastError(), "k_gmm_cov_reduce launch");
+static int launch_cov_reduce(int dev, const float *part, float *out, int64_t n, int chunks,
+                             void *stream) {
+    return launch(dev, n % 4 == 0 ? k_gmm_cov_reduce<true> : k_gmm_cov_reduce<false>,
+                  "k_gmm_cov_reduce launch", dim3((unsigned)((n + 1023) / 1024)), dim3(256), {0},
+                  stream, part, out, n, chunks);
 }
 
-static int launch_cov_reduce_upper(const float *part, float *out, int64_t n, int chunks, int d,
-                                   hipStream_t stream) {
-    const int K = (int)(n / ((int64_t)d * d)), ntu = (d / 32) * (d / 32 + 1) / 2;
-    const unsigned grid = (unsigned)(((int64_t)K * ntu * 256 + 255) / 256);
-    if (d == 64)
-        hipLaunchKernelGGL(k_gmm_cov_reduce_upper<64>, dim3(grid), dim3(256), 0, stream, part, out,
-                           n, chunks, K);
-    else
-        hipLaunchKernelGGL(k_gmm_cov_reduce_upper<128>, dim3(grid), dim3(256), 0, stream, part,
-                           out, n, chunks, K);
-    return hip_error(hipGetLastError(), "k_gmm_cov_reduce_upper launch");
+template <int D>
+static int launch_cov_reduce_upper(int dev, const float *part, float *out, int64_t n, int chunks,
+                                   void *stream) {
+    const int K = (int)(n / ((int64_t)D * D)), ntu = (D / 32) * (D / 32 + 1) / 2;
+    return launch(dev, k_gmm_cov_reduce_upper<D>, "k_gmm_cov_reduce_upper launch",
+                  dim3((unsigned)(((int64_t)K * ntu * 256 + 255) / 256)), dim3(256), {0}, stream,
+                  part, out, n, chunks, K);
 }
 
 // ---- M-step parameters + E-step constants (come_gmm_params) ----------------------------------
@@ -1302,70 +1268,53 @@ extern "C" int come_gmm_scatter(const float *x, int64_t V, int d, const float *r
     const bool mfma = (d == 64 || d == 128) && ((uintptr_t)x % 16) == 0;
     if (d > 128) {
         const int nt = (d + 63) / 64;
-        const size_t lds = sizeof(float) * ((size_t)kCovWideRB * d + kCovWideRB);
-        static bool attr_w = false;
-        if (!attr_w) {
-            (void)hipFuncSetAttribute((const void *)k_gmm_cov_wide,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr_w = true;
-        }
-        hipLaunchKernelGGL(k_gmm_cov_wide, dim3(K, used, nt * nt), dim3(kThreads), lds,
-                           (hipStream_t)stream, a);
-        rc = hip_error(hipGetLastError(), "k_gmm_cov_wide launch");
+        rc = launch(dev, k_gmm_cov_wide, "k_gmm_cov_wide launch", dim3(K, used, nt * nt),
+                    dim3(kThreads), {sizeof(float) * ((size_t)kCovWideRB * d + kCovWideRB)}, stream,
+                    a);
         if (rc || used == 1) return rc;
-        return launch_cov_reduce((const float *)scratch, scatter_out, n, used, (hipStream_t)stream);
+        return launch_cov_reduce(dev, scratch, scatter_out, n, used, stream);
     }
     // gmm_cov_async: 4 (default) = k_gmm_cov_fb3 at d = 128 / k_gmm_cov_bf3 at d = 64 (bf16 parts),
     // 5 = k_gmm_cov_bf3 at both widths, 3 = k_gmm_cov16 (fp32 16x16x4)
     const int cv = current_opts().gmm_cov_async;
     if (cv < 3 || cv > 5)
         return set_error(COME_E_INVALID, "gmm_cov_async must be 3, 4 or 5 (got %d)", cv);
+    if (!mfma) {
+        rc = launch(dev, k_gmm_cov_valu, "k_gmm_cov launch", dim3(K, used), dim3(256), {0}, stream,
+                    a);
+        if (rc || used == 1) return rc;
+        return launch_cov_reduce(dev, scratch, scatter_out, n, used, stream);
+    }
     // 4 at d = 128: k_gmm_cov_fb3 (its buffer descriptors span one chunk of x and of resp: each
     // under 2 GB, else k_gmm_cov_bf3); 4 at d = 64, and 5: k_gmm_cov_bf3
     const bool fb3_fits = per * std::max(d, K) * (int64_t)sizeof(float) < (int64_t(1) << 31);
-    if (mfma && cv == 4 && d == 128 && fb3_fits) {
-        static bool attr5 = false;
-        if (!attr5) {
-            (void)hipFuncSetAttribute((const void *)k_gmm_cov_fb3<128>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr5 = true;
-        }
+    if (cv == 4 && d == 128 && fb3_fits) {
+        using C = CovFb3<128>;
         a.upper_only = used > 1;
-        hipLaunchKernelGGL(k_gmm_cov_fb3<128>, dim3((K + CovFb3<128>::CPW - 1) / CovFb3<128>::CPW, used),
-                           dim3(CovFb3<128>::THREADS), CovFb3<128>::LDS_BYTES, (hipStream_t)stream, a);
-        rc = hip_error(hipGetLastError(), "k_gmm_cov_fb3 launch");
+        rc = launch(dev, k_gmm_cov_fb3<128>, "k_gmm_cov_fb3 launch",
+                    dim3((K + C::CPW - 1) / C::CPW, used), dim3(C::THREADS), {C::LDS_BYTES}, stream,
+                    a);
         if (rc || used == 1) return rc;
-        return launch_cov_reduce_upper((const float *)scratch, scatter_out, n, used, d,
-                                       (hipStream_t)stream);
+        return launch_cov_reduce_upper<128>(dev, scratch, scatter_out, n, used, stream);
     }
-    if (mfma && (cv == 4 || cv == 5)) {
-        static bool attr4 = false;
-        if (!attr4) {
-            for (void (*f)(CovArgs) : {k_gmm_cov_bf3<64>, k_gmm_cov_bf3<128>})
-                (void)hipFuncSetAttribute((const void *)f,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            attr4 = true;
+    return with_width(d, [&](auto width) {
+        constexpr int D = decltype(width)::value;
+        if (cv == 3) {
+            using C = Cov16<D>;
+            const int rc = launch(dev, k_gmm_cov16<D>, "k_gmm_cov launch",
+                                  dim3((K + C::CPW - 1) / C::CPW, used), dim3(C::THREADS), {0},
+                                  stream, a);
+            if (rc || used == 1) return rc;
+            return launch_cov_reduce(dev, scratch, scatter_out, n, used, stream);
         }
-        const int cpw = d == 64 ? CovBf3<64>::CPW : CovBf3<128>::CPW;
+        using C = CovBf3<D>;
         a.upper_only = used > 1;
-        hipLaunchKernelGGL(d == 64 ? k_gmm_cov_bf3<64> : k_gmm_cov_bf3<128>,
-                           dim3((K + cpw - 1) / cpw, used),
-                           dim3(d == 64 ? CovBf3<64>::THREADS : CovBf3<128>::THREADS),
-                           d == 64 ? CovBf3<64>::LDS_BYTES : CovBf3<128>::LDS_BYTES,
-                           (hipStream_t)stream, a);
-        rc = hip_error(hipGetLastError(), "k_gmm_cov_bf3 launch");
+        const int rc = launch(dev, k_gmm_cov_bf3<D>, "k_gmm_cov_bf3 launch",
+                              dim3((K + C::CPW - 1) / C::CPW, used), dim3(C::THREADS),
+                              {C::LDS_BYTES}, stream, a);
         if (rc || used == 1) return rc;
-        return launch_cov_reduce_upper((const float *)scratch, scatter_out, n, used, d,
-                                       (hipStream_t)stream);
-    }
-    void (*kern)(CovArgs) = !mfma ? k_gmm_cov_valu : (d == 64 ? k_gmm_cov16<64> : k_gmm_cov16<128>);
-    const int threads = !mfma ? 256 : (d == 64 ? Cov16<64>::THREADS : Cov16<128>::THREADS);
-    const int cpw = !mfma ? 1 : (d == 64 ? Cov16<64>::CPW : Cov16<128>::CPW);
-    hipLaunchKernelGGL(kern, dim3((K + cpw - 1) / cpw, used), dim3(threads), 0,
-                       (hipStream_t)stream, a);
-    rc = hip_error(hipGetLastError(), "k_gmm_cov launch");
-    if (rc || used == 1) return rc;
-    return launch_cov_reduce((const float *)scratch, scatter_out, n, used, (hipStream_t)stream);
+        return launch_cov_reduce_upper<D>(dev, scratch, scatter_out, n, used, stream);
+    });
 }
 
 extern "C" int come_gmm_params(const double *scatter, const double *nk, const double *means,
@@ -1380,21 +1329,11 @@ extern "C" int come_gmm_params(const double *scatter, const double *nk, const do
     int dev;
     int rc = ensure_init(&dev);
     if (rc) return rc;
-    static bool attr = false;
-    if (!attr) {
-        // (the kernel's static LDS, ~3 KB, counts against the 160 KB too: ask for what d = 128
-        // needs, 129 KB, not the whole of it -- a refused attribute would also leave an error
-        // for the launch check below to report)
-        rc = hip_error(hipFuncSetAttribute((const void *)k_gmm_params,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)(sizeof(double) * 128 * 129)),
-                       "k_gmm_params attribute");
-        if (rc) return rc;
-        attr = true;
-    }
     ParamsArgs p{scatter, nk, means, weights, K, d, reg_covar, cov_out, prec_chol_out,
                  e_prec_chol, e_mu_prec, e_log_norm, info};
-    hipLaunchKernelGGL(k_gmm_params, dim3(K), dim3(256), sizeof(double) * (size_t)d * (d + 1),
-                       (hipStream_t)stream, p);
-    return hip_error(hipGetLastError(), "k_gmm_params launch");
+    // (the kernel's static LDS, ~3 KB, counts against the 160 KB too: the limit asked for is what
+    // d = 128 needs, 129 KB, not the whole of it)
+    return launch(dev, k_gmm_params, "k_gmm_params launch", dim3(K), dim3(256),
+                  {sizeof(double) * (size_t)d * (d + 1), (int)(sizeof(double) * 128 * 129)}, stream,
+                  p);
 }

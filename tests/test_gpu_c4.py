@@ -12,6 +12,7 @@ import torch
 
 from come_amd import community_embeddings as ce
 from come_amd import gmm
+from come_amd._lib import options
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -46,18 +47,13 @@ def test_c4_community_grad_k50_1m(c4_rows, iters, kern):
     """x -= lr clip((beta/K) sum_k pi_ik inv_k (x_i - mu_k), +-5) (:61-78) on all 1M rows; 4,000
     sampled rows (incl. the first and last row tile) against float64, `iters` rounds;
     community_async 2 (fp32 16x16x4 MFMAs) and 3 (fp32 operands as bf16 parts), one tolerance."""
-    from come_amd import _lib
     x0, pi = c4_rows
     w, mu, cov = params(4)
     inv = np.linalg.inv(cov.astype(np.float32)).astype(np.float32)  # :36, fp32 inverse
     beta, lr = 2.0 * K, 0.1  # beta/K = 2: some entries reach the +-5 clip
     x = t(x0)
-    prev = _lib.launch_opts().community_async
-    _lib.set_option("community_async", kern)
-    try:
+    with options(community_async=kern):
         ce.community_grad(x, t(pi), t(mu), t(inv), beta, lr, iters)
-    finally:
-        _lib.set_option("community_async", prev)
     got = x.cpu().numpy()
     rng = np.random.RandomState(5)
     rows = np.concatenate([np.arange(64), rng.choice(len(x0), 3872, replace=False),
@@ -86,7 +82,6 @@ def test_c4_community_bf3_error_is_fp32_level(c4_rows):
     fp32 rounding, so its error against float64 must be that of the fp32-MFMA kernel
     (k_community16), not a reduced-precision one.  Unclipped update (beta/K = 0.5, lr = 1) on
     200k rows, all of them against float64: RMS and max error within 1.5x of k_community16's."""
-    from come_amd import _lib
     x0, pi = c4_rows[0][:200_000], c4_rows[1][:200_000]
     w, mu, cov = params(4)
     inv = np.linalg.inv(cov.astype(np.float32)).astype(np.float32)
@@ -100,17 +95,13 @@ def test_c4_community_bf3_error_is_fp32_level(c4_rows):
     assert np.abs(G).max() < 5  # no clipping: the step is the gradient itself
     step64 = -lr * G
     errs = {}
-    prev = _lib.launch_opts().community_async
-    try:
-        for kern in (2, 3):
-            _lib.set_option("community_async", kern)
-            x = t(x0)
+    for kern in (2, 3):
+        x = t(x0)
+        with options(community_async=kern):
             ce.community_grad(x, t(pi), t(mu), t(inv), beta, lr, 1)
-            e = (x.cpu().numpy().astype(np.float64) - X) - step64
-            errs[kern] = (np.sqrt((e ** 2).mean() / (step64 ** 2).mean()),
-                          np.abs(e).max() / np.abs(step64).max())
-    finally:
-        _lib.set_option("community_async", prev)
+        e = (x.cpu().numpy().astype(np.float64) - X) - step64
+        errs[kern] = (np.sqrt((e ** 2).mean() / (step64 ** 2).mean()),
+                      np.abs(e).max() / np.abs(step64).max())
     print("rms / max relative error vs float64: fp32 MFMA %.3g / %.3g, bf16 parts %.3g / %.3g"
           % (errs[2] + errs[3]))
     assert errs[3][0] <= 1.5 * errs[2][0] and errs[3][1] <= 1.5 * errs[2][1], errs
@@ -122,20 +113,14 @@ def test_c4_responsibilities_k50_1m(c4_rows, r16):
     sklearn's upper-triangular precision factors) and the EM E-step (come_gmm_estep, + per-row
     log-sum-exp) on 4,000 sampled rows against the float64 restatement of sklearn;
     gmm_resp16 2 (fp32 16x16x4 MFMAs) and 3 (fp32 operands as bf16 parts), one tolerance."""
-    from come_amd import _lib
-    prev = _lib.launch_opts().gmm_resp16
-    _lib.set_option("gmm_resp16", r16)
-    try:
+    with options(gmm_resp16=r16):
         _c4_responsibilities(c4_rows)
-    finally:
-        _lib.set_option("gmm_resp16", prev)
 
 
 def test_c4_estep_bf3_error_is_fp32_level(c4_rows):
     """k_gmm_resp_b16's per-row log-sum-exp (the EM log-likelihood term) against float64 on 100k
     C4 rows: RMS and max error within 1.5x of the fp32-MFMA E-step's (k_gmm_resp16t) -- the
     bf16-part products are not a reduced-precision form (see the community test above)."""
-    from come_amd import _lib
     from scipy.special import logsumexp
     x0 = c4_rows[0][:100_000]
     w, mu, cov = params(6, sep=0.3)
@@ -150,15 +135,11 @@ def test_c4_estep_bf3_error_is_fp32_level(c4_rows):
     lp = np.stack([lnf[k] - 0.5 * ((X @ pcf[k] - mpf[k]) ** 2).sum(1) for k in range(K)], 1)
     ref = logsumexp(lp, 1)
     errs = {}
-    prev = _lib.launch_opts().gmm_resp16
-    try:
-        for r16 in (2, 3):
-            _lib.set_option("gmm_resp16", r16)
+    for r16 in (2, 3):
+        with options(gmm_resp16=r16):
             _, lse = gmm.estep(t(x0), g._e_pc, g._e_mp, g._e_ln)
-            e = lse.double().cpu().numpy() - ref
-            errs[r16] = (np.sqrt((e ** 2).mean() / (ref ** 2).mean()), np.abs(e).max())
-    finally:
-        _lib.set_option("gmm_resp16", prev)
+        e = lse.double().cpu().numpy() - ref
+        errs[r16] = (np.sqrt((e ** 2).mean() / (ref ** 2).mean()), np.abs(e).max())
     print("lse rms relative / max abs error vs float64: fp32 MFMA %.3g / %.3g, bf16 parts "
           "%.3g / %.3g" % (errs[2] + errs[3]))
     assert errs[3][0] <= 1.5 * errs[2][0] and errs[3][1] <= 1.5 * errs[2][1], errs
@@ -207,16 +188,11 @@ def test_c4_scatter_k50(c4_100k, cov):
     members of a workgroup pair included; gmm_cov_async 3 (fp32 16x16x4), 4 (bf16 parts, the
     staging inside the MFMA wavefronts: k_gmm_cov_fb3) and 5 (bf16 parts, specialised staging
     wavefronts: k_gmm_cov_bf3)."""
-    from come_amd import _lib
     X, w, mu, cov_ = c4_100k
     R = np.random.RandomState(10).dirichlet(np.ones(K), len(X)).astype(np.float32)
     M = (mu + 0.1).astype(np.float32)
-    prev = _lib.launch_opts().gmm_cov_async
-    _lib.set_option("gmm_cov_async", cov)
-    try:
+    with options(gmm_cov_async=cov):
         S = gmm.scatter(t(X), t(R), t(M)).cpu().numpy()
-    finally:
-        _lib.set_option("gmm_cov_async", prev)
     X64 = X.astype(np.float64)
     for k in (0, 1, 24, 25, 48, 49):
         Dk = X64 - M[k]
@@ -229,22 +205,17 @@ def test_c4_scatter_bf3_error_is_fp32_level(c4_100k):
     """k_gmm_cov_fb3 and k_gmm_cov_bf3 (E^T E with E = sqrt(r) (x - m) carried as three bf16
     parts) against float64 on the 100k C4 rows, all 50 components: RMS and max relative error
     within 1.5x of the fp32-MFMA scatter's (k_gmm_cov16)."""
-    from come_amd import _lib
     X, w, mu, cov_ = c4_100k
     R = np.random.RandomState(10).dirichlet(np.ones(K), len(X)).astype(np.float32)
     M = (mu + 0.1).astype(np.float32)
     X64 = X.astype(np.float64)
     ref = np.stack([((R[:, k, None] * (X64 - M[k])).T @ (X64 - M[k])) for k in range(K)])
     errs = {}
-    prev = _lib.launch_opts().gmm_cov_async
-    try:
-        for cv in (3, 4, 5):
-            _lib.set_option("gmm_cov_async", cv)
+    for cv in (3, 4, 5):
+        with options(gmm_cov_async=cv):
             e = gmm.scatter(t(X), t(R), t(M)).double().cpu().numpy() - ref
-            errs[cv] = (np.sqrt((e ** 2).mean() / (ref ** 2).mean()),
-                        np.abs(e).max() / np.abs(ref).max())
-    finally:
-        _lib.set_option("gmm_cov_async", prev)
+        errs[cv] = (np.sqrt((e ** 2).mean() / (ref ** 2).mean()),
+                    np.abs(e).max() / np.abs(ref).max())
     print("scatter rms / max relative error vs float64: fp32 MFMA %.3g / %.3g, bf16 parts "
           "(fb3) %.3g / %.3g, (bf3) %.3g / %.3g" % (errs[3] + errs[4] + errs[5]))
     for cv in (4, 5):
@@ -263,19 +234,14 @@ def test_scatter_fused_matches_bf3(V, K_, chunks):
     and both match float64.  Ragged chunks (rows not a multiple of the 16-row block or of the
     staging ring), an odd K (a workgroup with one live component), a single chunk, more chunks than
     rows, and gmm.scatter's own chunking."""
-    from come_amd import _lib
     rng = np.random.RandomState(V)
     X = rng.standard_normal((V, D)).astype(np.float32)
     R = rng.dirichlet(np.ones(K_), V).astype(np.float32)
     M = (rng.standard_normal((K_, D)) * 0.5).astype(np.float32)
     out = {}
-    prev = _lib.launch_opts().gmm_cov_async
-    try:
-        for cv in (4, 5):
-            _lib.set_option("gmm_cov_async", cv)
+    for cv in (4, 5):
+        with options(gmm_cov_async=cv):
             out[cv] = gmm.scatter(t(X), t(R), t(M), chunks=chunks or None).cpu().numpy()
-    finally:
-        _lib.set_option("gmm_cov_async", prev)
     for k in range(K_):
         scale = np.abs(out[5][k]).max()
         np.testing.assert_allclose(out[4][k], out[5][k], rtol=0, atol=2e-6 * scale)

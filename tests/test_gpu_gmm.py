@@ -15,29 +15,11 @@ import numpy as np
 import pytest
 
 from come_amd import gmm
+from come_amd._lib import options
 from oracle import oracle as orc
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-
-class opts(object):
-    """Process-wide launch options set for a block and restored afterwards."""
-
-    def __init__(self, **kv):
-        self.kv = kv
-
-    def __enter__(self):
-        from come_amd import _lib
-        cur = _lib.launch_opts()
-        self.old = {k: getattr(cur, k) for k in self.kv}
-        for k, v in self.kv.items():
-            _lib.set_option(k, v)
-
-    def __exit__(self, *exc):
-        from come_amd import _lib
-        for k, v in self.old.items():
-            _lib.set_option(k, v)
 
 
 def dev():
@@ -60,6 +42,15 @@ def problem(V, K, d, seed, sep=3.0):
     return X.astype(np.float32), w, mu, cov
 
 
+def _estep_reference(X, w, mu, cov):
+    """(responsibilities, per-row log sum_k w_k N(x; mu_k, S_k)) in float64."""
+    from scipy.special import logsumexp
+    from scipy.stats import multivariate_normal
+    lp = np.stack([np.log(w[k]) + multivariate_normal(mu[k], cov[k]).logpdf(X.astype(np.float64))
+                   for k in range(len(w))], 1)
+    return np.exp(orc.gmm_log_resp(X.astype(np.float64), w, mu, cov)), logsumexp(lp, 1)
+
+
 @pytest.mark.parametrize("V,K,d", [(1000, 4, 8), (3000, 6, 64), (2500, 5, 128), (777, 3, 100),
                                    (900, 4, 256), (300, 70, 200)])
 def test_estep_vs_numpy(V, K, d):
@@ -70,14 +61,61 @@ def test_estep_vs_numpy(V, K, d):
     g._w, g._mu, g._pc = t(w), t(mu), t(pc)
     g._prepare_estep()
     resp, lse = gmm.estep(t(X), g._e_pc, g._e_mp, g._e_ln)
-    ref_lr = orc.gmm_log_resp(X.astype(np.float64), w, mu, cov)
-    np.testing.assert_allclose(resp.cpu().numpy(), np.exp(ref_lr), atol=2e-4)
-    # lse: log sum_k w_k N(x; mu_k, S_k), float64 reference
-    from scipy.special import logsumexp
-    from scipy.stats import multivariate_normal
-    lp = np.stack([np.log(w[k]) + multivariate_normal(mu[k], cov[k]).logpdf(X.astype(np.float64))
-                   for k in range(K)], 1)
-    np.testing.assert_allclose(lse.cpu().numpy(), logsumexp(lp, 1), rtol=2e-5, atol=2e-3)
+    ref_resp, ref_lse = _estep_reference(X, w, mu, cov)
+    np.testing.assert_allclose(resp.cpu().numpy(), ref_resp, atol=2e-4)
+    np.testing.assert_allclose(lse.cpu().numpy(), ref_lse, rtol=2e-5, atol=2e-3)
+
+
+@pytest.mark.parametrize("d", [64, 128])
+def test_unaligned_operands_take_the_valu_kernels(d):
+    """At d = 64 / 128 an operand that is not 16-byte aligned sends the call to the VALU kernel
+    (the MFMA kernels load it 16 bytes at a time): prec_chol for the E-step (k_gmm_resp), X for the
+    scatter (k_gmm_cov_valu), inv_cov for the community step (k_community_grad).  Each operand is a
+    contiguous view at element offset 1 of a larger fp32 buffer; inputs, references and tolerances
+    are those the VALU kernels are held to at other widths (test_estep_vs_numpy,
+    test_scatter_vs_numpy, tests/test_gpu_parity.py::test_community_grad_vs_oracle)."""
+    from come_amd import community_embeddings as ce
+    V, K = 300, 3
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32), device=dev())  # noqa: E731
+
+    def off1(a):
+        v = torch.empty(a.numel() + 1, dtype=torch.float32, device=a.device)[1:].view(a.shape)
+        v.copy_(a)
+        assert v.is_contiguous() and v.data_ptr() % 16 == 4
+        return v
+
+    X, w, mu, cov = problem(V, K, d, V + d)
+    g = gmm.GaussianMixture(K)
+    g._w, g._mu, g._pc = (torch.as_tensor(a, device=dev()) for a in
+                          (w, mu, orc.precision_cholesky(cov)))
+    g._prepare_estep()
+    resp, lse = gmm.estep(t(X), off1(g._e_pc), g._e_mp, g._e_ln)
+    ref_resp, ref_lse = _estep_reference(X, w, mu, cov)
+    np.testing.assert_allclose(resp.cpu().numpy(), ref_resp, atol=2e-4)
+    np.testing.assert_allclose(lse.cpu().numpy(), ref_lse, rtol=2e-5, atol=2e-3)
+
+    rng = np.random.RandomState(V + K)
+    X = rng.normal(size=(V, d)).astype(np.float32)
+    R = rng.dirichlet(np.ones(K), V).astype(np.float32)
+    M = rng.normal(size=(K, d)).astype(np.float32)
+    S = gmm.scatter(off1(t(X)), t(R), t(M)).cpu().numpy()
+    for k in range(K):
+        D = X.astype(np.float64) - M[k]
+        ref = (R[:, k, None] * D).T @ D
+        np.testing.assert_allclose(S[k], ref, rtol=1e-4, atol=1e-4 * np.abs(ref).max())
+
+    rng = np.random.RandomState(d + V)
+    x0 = rng.normal(size=(V, d)).astype(np.float32)
+    A = rng.normal(size=(K, d, d)) / np.sqrt(d)
+    cov = np.einsum("kij,klj->kil", A, A) + np.eye(d)[None] * 0.5
+    inv = np.linalg.inv(cov.astype(np.float32)).astype(np.float32)
+    mu = rng.normal(size=(K, d)).astype(np.float32)
+    pi = rng.dirichlet(np.ones(K), V).astype(np.float32)
+    for beta in (0.05, 40.0):  # (the second reaches the clip at +-5)
+        x = t(x0)
+        ce.community_grad(x, t(pi), t(mu), off1(t(inv)), beta, 0.1, 2)
+        ref = orc.community_train(x0, pi, mu, inv, beta, 0.1, 2)
+        np.testing.assert_allclose(x.cpu().numpy(), ref, rtol=2e-5, atol=2e-5)
 
 
 @pytest.mark.parametrize("d", [64, 128])
@@ -102,7 +140,7 @@ def test_estep_mixed_factor_shapes(d, r16):
     ln = np.log(np.full(K, 1.0 / K))
     mp = np.einsum("kd,kde->ke", mu.astype(np.float64), P)
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32), device=dev())  # noqa: E731
-    with opts(gmm_resp16=r16):
+    with options(gmm_resp16=r16):
         resp, lse = gmm.estep(t(X), t(P), t(mp), t(ln))
     Y = np.einsum("vd,kde->vke", X.astype(np.float64), P) - mp[None]
     lp = ln[None] - 0.5 * (Y ** 2).sum(-1)
@@ -128,7 +166,7 @@ def test_estep_default_and_fallback_agree(V, K, d):
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32), device=dev())  # noqa: E731
     out = {}
     for r16 in (3, 2):
-        with opts(gmm_resp16=r16):
+        with options(gmm_resp16=r16):
             resp, lse = gmm.estep(t(X), t(P), t(mp), t(ln))
         out[r16] = resp.cpu().numpy(), lse.cpu().numpy()
         assert np.isfinite(out[r16][0]).all() and np.abs(out[r16][0].sum(1) - 1).max() < 1e-4
@@ -150,15 +188,15 @@ def test_variant_options_outside_the_kept_set_are_rejected():
     mp, ln = t(np.zeros((K, d))), t(np.log(np.full(K, 1.0 / K)))
     R = t(rng.dirichlet(np.ones(K), V))
     for bad in (0, 1, 4, 7, 16, 19):
-        with opts(gmm_resp16=bad):
+        with options(gmm_resp16=bad):
             with pytest.raises(_lib.ComeError, match="gmm_resp16"):
                 gmm.estep(X, P, mp, ln)
     for bad in (0, 1, 2, 6):
-        with opts(gmm_cov_async=bad):
+        with options(gmm_cov_async=bad):
             with pytest.raises(_lib.ComeError, match="gmm_cov_async"):
                 gmm.scatter(X, R, mp)
     for bad in (0, 1, 4):
-        with opts(community_async=bad):
+        with options(community_async=bad):
             with pytest.raises(_lib.ComeError, match="community_async"):
                 ce.community_grad(X.clone(), R, mp, P, 0.01, 0.1, 1)
 
@@ -172,7 +210,7 @@ def test_scatter_vs_numpy(V, K, d, chunks, cov):
     X = rng.normal(size=(V, d)).astype(np.float32)
     R = rng.dirichlet(np.ones(K), V).astype(np.float32)
     M = rng.normal(size=(K, d)).astype(np.float32)
-    with opts(gmm_cov_async=cov):
+    with options(gmm_cov_async=cov):
         S = gmm.scatter(torch.as_tensor(X, device=dev()), torch.as_tensor(R, device=dev()),
                         torch.as_tensor(M, device=dev()), chunks=chunks).cpu().numpy()
     X64 = X.astype(np.float64)
@@ -279,7 +317,7 @@ def test_scatter_default_and_fallback_agree(V, K, d, chunks):
     mu = t(rng.standard_normal((K, d)).astype(np.float32))
     out = []
     for opt in (3, 4, 5):
-        with opts(gmm_cov_async=opt):
+        with options(gmm_cov_async=opt):
             out.append(gmm.scatter(x, resp, mu, chunks=chunks).cpu().numpy())
     for o in out[1:]:
         np.testing.assert_allclose(o, out[0], rtol=0, atol=1e-5 * np.abs(out[0]).max())
@@ -328,7 +366,7 @@ def test_estep_upper_factors_vs_float64(V, K, d, r16):
     mp = np.einsum("kd,kde->ke", mu, P)
     ln = np.log(rng.dirichlet(np.ones(K)))
     t = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32), device=dev())  # noqa: E731
-    with opts(gmm_resp16=r16):
+    with options(gmm_resp16=r16):
         resp, lse = gmm.estep(t(X), t(P), t(mp), t(ln))
     Y = np.einsum("vd,kde->vke", X.astype(np.float64), P.astype(np.float32).astype(np.float64)) \
         - mp.astype(np.float32)[None]

@@ -24,6 +24,7 @@ from oracle import oracle as orc
 
 import come_amd.training_sdg_inner as tsi
 from come_amd import community_embeddings as ce
+from come_amd._lib import options
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -329,7 +330,6 @@ def test_o1_random_bit_exact_vs_oracle(d, neg, V, E, chunk):
     k_sgns_o1_runs (o1_chunk = 7: the input row held over runs of edges sharing it; edges sorted
     by their first endpoint so runs form, self-loops and negatives equal to the held row
     included; o1_chunk = -1, the default: one chunk of every edge in order)."""
-    from come_amd import _lib
     rng = np.random.RandomState(d + neg + V)
     table = orc.make_table(rng.randint(1, 30, V), 5 * V + 7)
     node0 = rng.uniform(-0.5, 0.5, (V, d)).astype(np.float32)
@@ -338,12 +338,8 @@ def test_o1_random_bit_exact_vs_oracle(d, neg, V, E, chunk):
     if chunk:
         edges = edges[np.argsort(edges[:, 0], kind="stable")]
     seeds = rng.randint(0, 2 ** 48, E, dtype=np.int64).astype(np.uint64)
-    prev = _lib.launch_opts().o1_chunk
-    _lib.set_option("o1_chunk", chunk)
-    try:
+    with options(o1_chunk=chunk):
         node = run_o1(node0, edges, seeds, neg, table, 0.2)
-    finally:
-        _lib.set_option("o1_chunk", prev)
     n_ref = node0.copy()
     orc.sgns_o1(n_ref, edges, seeds, neg, table, 0.2, dot_mode=orc.DOT_WAVE64)
     np.testing.assert_array_equal(node, n_ref)
@@ -393,13 +389,8 @@ def test_community_grad_vs_oracle(d, V, K, iters, kern):
     (d = 96) and the wide VALU path (d = 256, 500: matrices streamed in row chunks) against the
     numpy restatement of community_embeddings.py:61-78: fp32 contractions in another order,
     rtol/atol 2e-5; the clip at +-5 is exercised (beta large)."""
-    from come_amd import _lib
-    prev = _lib.launch_opts().community_async
-    _lib.set_option("community_async", kern)
-    try:
+    with options(community_async=kern):
         _community_vs_oracle(d, V, K, iters)
-    finally:
-        _lib.set_option("community_async", prev)
 
 
 def _community_vs_oracle(d, V, K, iters):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from come_amd import graph_utils as gu
+from come_amd._lib import options
 from come_amd.graph import chung_lu
 
 torch = pytest.importorskip("torch")
@@ -117,7 +118,6 @@ def test_staged_output_matches_direct_stores(P, L):
     """k_random_walks_staged (LDS-staged, coalesced row segments) vs k_random_walks (one store
     per lane per step): the same Philox counters, so the walks must be identical -- including
     invalid starts, dead ends (a node without neighbours), emit and ragged P / L."""
-    from come_amd import _lib
     d = dev()
     g = chung_lu(2000, 5.0, seed=P + L)
     rowptr = np.concatenate([g.rowptr, [g.rowptr[-1]] * 3])  # 3 isolated nodes at the end
@@ -130,19 +130,16 @@ def test_staged_output_matches_direct_stores(P, L):
     s[::11] = -1  # not a node: an empty walk
     starts = torch.from_numpy(s).to(d)
     emit = (torch.arange(V, device=d, dtype=torch.int32) * 5 + 2).contiguous()
-    try:
-        for kw in ({}, {"emit": emit}):
-            out = []
-            for opt in (0, 1, 2, 3):  # direct, then 16-, 8- and 32-step LDS slices
-                _lib.set_option("walk_staged", opt)
+    for kw in ({}, {"emit": emit}):
+        out = []
+        for opt in (0, 1, 2, 3):  # direct, then 16-, 8- and 32-step LDS slices
+            with options(walk_staged=opt):
                 out.append(gu.device_walks(rowptr_t, col, starts, L, alpha=0.15, seed=7,
                                            walk_offset=5, **kw))
-            for o in out[1:]:
-                assert torch.equal(out[0], o), (P, L, kw.keys())
-            w = out[1].cpu().numpy()
-            assert (w[::11] == -1).all()
-    finally:
-        _lib.set_option("walk_staged", 1)  # the default
+        for o in out[1:]:
+            assert torch.equal(out[0], o), (P, L, kw.keys())
+        w = out[1].cpu().numpy()
+        assert (w[::11] == -1).all()
 
 
 @pytest.mark.parametrize("alpha,L,offset", [(0.0, 80, 0), (0.15, 33, 5_000_000_123), (1.0, 7, 5)])
