@@ -14,6 +14,10 @@
                   (8.6 TB/s; 24 algorithmic B per step reported beside it).  CPU baseline: the exact
                   CPython-stream walker (come_walks_reference, native restatement of
                   graph_utils.build_deepwalk_corpus) on host threads.
+  --workload kmeans  the k-means initialisation of the C4 GMM fit (1M rows, K=50, d=128): ms per
+                  Lloyd iteration of the torch path and of the native kernels (come_amd.kmeans) from
+                  the same centres, both seedings, a full KMeans.fit, and the k-means share of a
+                  GaussianMixture fit with each kmeans_backend; roofline: X read once against HBM.
 Each prints one JSON line.  CPU baselines on a bounded sample: O1 the builder's Hogwild C
 restatement of train_o1 (oracle/come_oracle_mt.c; reported beside it as the reference-equivalent
 rate, restatement / its calibrated speed-up over the reference's GIL-bound Node2Vec.train,
@@ -368,6 +372,128 @@ def walks(args):
         "cpu_baseline": cpu}))
 
 
+def kmeans_bench(args):
+    """The k-means initialisation of the C4 GMM fit (V rows, K clusters, d features): one Lloyd
+    iteration of the torch path (GaussianMixture._kmeans_labels' arithmetic: distance matrix,
+    argmin, bincount, index_add_, centre update and the host read of the shift) against the native
+    one (come_kmeans_lloyd + come_kmeans_update, the shift read every fourth iteration as
+    come_amd.kmeans.KMeans runs it), both from the same seeded centres over the same number of
+    iterations; the seeding of both; a full KMeans.fit; and the k-means share of a
+    GaussianMixture fit with each backend."""
+    import torch
+    from come_amd import gmm, kmeans
+    dev = torch.device("cuda", 0)
+    V, K, d = args.nodes, args.k, args.dim
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    mu = torch.randn((K, d), generator=g, device=dev) * 0.5
+    lab = torch.randint(0, K, (V,), generator=g, device=dev)
+    X = (mu[lab] + torch.randn((V, d), generator=g, device=dev)).contiguous()
+    del lab
+    xx = (X * X).sum(1)
+
+    def wall(fn, reps=1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps * 1e3, out
+
+    def gens():
+        a = torch.Generator(device=dev)
+        a.manual_seed(11)
+        return a
+    gm = gmm.GaussianMixture(K)
+    gm._kmeans_plusplus(X[:4096].contiguous(), xx[:4096].contiguous(), gens())  # warm-up
+    kmeans.kmeans_plusplus(X[:4096].contiguous(), xx[:4096].contiguous(), K, gens())
+    seed_torch_ms, C0 = wall(lambda: gm._kmeans_plusplus(X, xx, gens()))
+    seed_native_ms, C1 = wall(lambda: kmeans.kmeans_plusplus(X, xx, K, gens()))
+    same_seeds = bool(torch.equal(C0, C1))
+    C0 = C0.contiguous()
+
+    def torch_iter(C):  # gmm.py _kmeans_labels, one iteration
+        dist_ = xx[:, None] - 2 * X @ C.t() + (C * C).sum(1)[None]
+        labels = torch.argmin(dist_, 1)
+        cnt = torch.bincount(labels, minlength=K).float()
+        S = torch.zeros((K, d), dtype=torch.float32, device=X.device)
+        S.index_add_(0, labels, X)
+        newC = torch.where(cnt[:, None] > 0, S / cnt.clamp_min(1)[:, None], C)
+        float(((newC - C) ** 2).sum())
+        return newC
+
+    def run_torch(n):
+        C = C0
+        for _ in range(n):
+            C = torch_iter(C)
+        return C
+
+    def run_native(n):
+        C = C0.clone()
+        for i in range(1, n + 1):
+            _, sums, counts, _ = kmeans.accumulate(X, C)
+            shift2 = kmeans.update(C, sums, counts)
+            if i % 4 == 0:
+                float(shift2)
+        return C
+    run_torch(args.warmup)
+    run_native(args.warmup)
+    t_torch, Ct = wall(lambda: run_torch(args.steps))
+    t_native, Cn = wall(lambda: run_native(args.steps))
+    t_torch /= args.steps
+    t_native /= args.steps
+    centre_diff = float((Ct - Cn).abs().max())
+    Cf = C0.clone()
+    _, ks = timed(lambda: kmeans.accumulate(X, Cf), args.steps, args.warmup)
+    t_kernel = float(np.mean(ks))
+    log("torch %.3f ms / iteration, native %.3f ms (lloyd + reduce launches alone %.3f ms)" % (
+        t_torch, t_native, t_kernel))
+    fit_ms, km = wall(lambda: kmeans.KMeans(K, random_state=0).fit(X))
+    shares = {}
+    for backend in ("torch", "native"):
+        gmm.GaussianMixture(K, reg_covar=1e-5, max_iter=2, random_state=0, kmeans_max_iter=2,
+                            kmeans_backend=backend).fit(X)  # warm-up: library scratch, BLAS
+        m = gmm.GaussianMixture(K, reg_covar=1e-5, n_init=1, random_state=0,
+                                kmeans_backend=backend)
+        spent = [0.0]
+        inner = m._kmeans_labels
+
+        def timed_init(X_, gen_, inner=inner, spent=spent):
+            ms, out = wall(lambda: inner(X_, gen_))
+            spent[0] += ms
+            return out
+        m._kmeans_labels = timed_init
+        total_ms, _ = wall(lambda: m.fit(X))
+        shares[backend] = {"fit_ms": total_ms, "kmeans_ms": spent[0],
+                           "kmeans_share": spent[0] / total_ms, "em_iterations": int(m.n_iter_),
+                           "lower_bound": float(m.lower_bound_)}
+        log("GaussianMixture fit, kmeans_backend=%s: %.0f ms, k-means %.0f ms" % (
+            backend, total_ms, spent[0]))
+    mfma_flops = 2.0 * 2 * V * 64 * d  # scores and one-hot sums, K padded to 64
+    print(json.dumps({
+        "metric": "k-means Lloyd iteration, %d rows K=%d d=%d" % (V, K, d),
+        "value": t_native, "unit": "ms per Lloyd iteration (native)", "n_gpus": 1,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": t_native,
+        "higher_is_better": False, "dtype": "f32",
+        "data": "synthetic: %d centres 0.5 N(0,1), unit noise" % K,
+        "config": {"workload": "k-means init of the C4 GMM fit: V=%d K=%d d=%d" % (V, K, d),
+                   "torch_iteration_ms": t_torch, "native_iteration_ms": t_native,
+                   "speedup_vs_torch_iteration": t_torch / t_native,
+                   "native_lloyd_launches_ms": t_kernel,
+                   "max_centre_difference_after_%d_iterations" % args.steps: centre_diff,
+                   "seeding_torch_ms": seed_torch_ms, "seeding_native_ms": seed_native_ms,
+                   "seedings_identical": same_seeds,
+                   "kmeans_fit_ms": fit_ms, "kmeans_fit_n_iter": int(km.n_iter_),
+                   "kmeans_fit_seeding_share": seed_native_ms / fit_ms,
+                   "gaussian_mixture_fit": shares},
+        "roofline": {"bound": "hbm", "achieved": V * d * 4 / (t_kernel / 1e3) / 1e9,
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": V * d * 4 / (t_kernel / 1e3) / 1e9 / HBM_PEAK_GBS,
+                     "fp32_mfma_frac": mfma_flops / (t_kernel / 1e3) / 1e12 / F32_MFMA_PEAK_TFLOPS,
+                     "mfma_flops_per_iteration": mfma_flops, "avg_kernel_ms": t_kernel},
+        "cpu_baseline": None}))
+
+
 def blas_threads():
     """Threads of the BLAS pool numpy / scipy / sklearn run on in this process (threadpoolctl),
     None if it cannot tell."""
@@ -381,7 +507,7 @@ def blas_threads():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["c2", "c4", "walks"], required=True)
+    ap.add_argument("--workload", choices=["c2", "c4", "walks", "kmeans"], required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dim", type=int, default=128)
@@ -410,7 +536,7 @@ def main():
         for kv in args.opt:
             k, v = kv.split("=")
             _lib.set_option(k, int(v))
-    {"c2": c2, "c4": c4, "walks": walks}[args.workload](args)
+    {"c2": c2, "c4": c4, "walks": walks, "kmeans": kmeans_bench}[args.workload](args)
 
 
 if __name__ == "__main__":

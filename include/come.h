@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-/* ABI 5 (this header): "gmm_cov_async" accepts 3 / 4 / 5.  Its default 4 now runs k_gmm_cov_fb3 at
+/* ABI 5, additive (the version is unchanged: nothing that existed moved): come_kmeans_scratch,
+ * come_kmeans_lloyd, come_kmeans_assign and come_kmeans_update (k-means for the GMM init and
+ * come_amd.kmeans.KMeans).
+ * ABI 5 (this header): "gmm_cov_async" accepts 3 / 4 / 5.  Its default 4 now runs k_gmm_cov_fb3 at
  * d = 128 (the staging inside the MFMA wavefronts; the diagonal 32x32 tiles' cross terms taken as
  * U + U^T, so their fp32 rounding differs from ABI 4's at the same fp32-level error; off-diagonal
  * tiles are bit-identical) and k_gmm_cov_bf3 at d = 64; 5 runs ABI 4's k_gmm_cov_bf3 at both widths.
@@ -181,6 +184,44 @@ int come_gmm_params(const double *scatter, const double *nk, const double *means
                     const double *weights, int K, int d, double reg_covar, double *cov_out,
                     double *prec_chol_out, float *e_prec_chol, float *e_mu_prec,
                     float *e_log_norm, int *info, void *stream);
+
+/* ---- k-means (Lloyd): the GMM's initialisation (sklearn KMeans inside GaussianMixture, reference
+ * community_embeddings.py:27) and come_amd.kmeans.KMeans ----
+ * x [V x d] rows, centers [K x d] (device fp32).  1 <= d <= 512; 1 <= K <= 64, K <= 4096 for
+ * d = 64, 128 and d > 128 (GaussianMixture's limits).  A row's label is the argmax over k of
+ * s_k = x . c_k - |c_k|^2 / 2 (= the argmin of the squared distance), ties to the lowest k;
+ * mindist = max(0, |x|^2 - 2 s_label).  d = 64, 128 with K <= 64 and 16-byte aligned x and
+ * centers run on fp32 MFMAs (scores, and the cluster sums as a one-hot x X product), anything else
+ * on a VALU kernel.  No float atomics: every output is bit-identical from run to run.
+ *
+ * come_kmeans_scratch (host): the row chunking of come_kmeans_lloyd for a device with `cus` compute
+ * units (<= 0: 256): chunks_out >= 1 with chunks * K * d * 4 <= 128 MB, and rows_per_chunk_out, an
+ * upper bound on the rows whose cluster sums are accumulated in fp32 before the float64 reduction
+ * (a multiple of 16).  V must be >= 1.  The scratch of come_kmeans_lloyd is
+ * chunks * (8 + 4 K d + 4 K) bytes, 8-byte aligned.
+ *
+ * come_kmeans_lloyd: one pass over x: labels_out [V] (int32), mindist_out [V] (optional), and the
+ * per-chunk partial sums / counts / inertia into `scratch`, reduced in chunk order into sums_out
+ * [K x d] (float64: sum of the rows of each cluster), counts_out [K] (int64) and inertia_out
+ * (float64: the sum of mindist, accumulated in float64).  V must be >= 1 (an empty pass would
+ * still have to write its outputs).
+ *
+ * come_kmeans_assign: labels_out and (optionally) mindist_out only, by the same arithmetic.
+ * V = 0 is a no-op returning 0.
+ *
+ * come_kmeans_update: centers_k = (float)(sums_k / counts_k) in place; a cluster with count 0 keeps
+ * its centre bit for bit.  stats2[0] = sum (new - old)^2 in float64 (stats2[1] is not written).
+ * Reduction and update are separate so that a distributed fit can all-reduce sums and counts
+ * between them. */
+int come_kmeans_scratch(int64_t V, int d, int K, int cus, int *chunks_out,
+                        int *rows_per_chunk_out);
+int come_kmeans_lloyd(const float *x, int64_t V, int d, const float *centers, int K, int chunks,
+                      void *scratch, int32_t *labels_out, float *mindist_out, double *sums_out,
+                      int64_t *counts_out, double *inertia_out, void *stream);
+int come_kmeans_assign(const float *x, int64_t V, int d, const float *centers, int K,
+                       int32_t *labels_out, float *mindist_out, void *stream);
+int come_kmeans_update(float *centers, const double *sums, const int64_t *counts, int K, int d,
+                       double *stats2, void *stream);
 
 /* ---- Random walks: the producer of train_o2's input (utils/graph_utils.py) ----
  * Graphs are CSR over node POSITIONS 0..V-1 in networkx order (see come_graph_from_edges):

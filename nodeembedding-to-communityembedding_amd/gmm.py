@@ -167,7 +167,10 @@ class GaussianMixture(object):
     def __init__(self, n_components=1, covariance_type='full', tol=1e-3, reg_covar=1e-6,
                  max_iter=100, n_init=1, init_params='kmeans', weights_init=None,
                  means_init=None, precisions_init=None, random_state=None, kmeans_max_iter=300,
-                 kmeans_tol=1e-4, device=None, distributed=False, group=None):
+                 kmeans_tol=1e-4, device=None, distributed=False, group=None,
+                 kmeans_backend='torch'):
+        if kmeans_backend not in ('torch', 'native'):
+            raise ValueError("kmeans_backend must be 'torch' or 'native'")
         if covariance_type != 'full':
             raise NotImplementedError("only covariance_type='full' (the reference's) is "
                                       "implemented")
@@ -189,6 +192,7 @@ class GaussianMixture(object):
         self.device = device
         self.distributed = bool(distributed)
         self.group = group
+        self.kmeans_backend = kmeans_backend
 
     def _rank_world(self):
         return world_of(self.group) if self.distributed else (0, 1)
@@ -312,8 +316,15 @@ class GaussianMixture(object):
     def _kmeans_labels(self, X, gen):
         """KMeans(n_clusters=K, n_init=1): greedy k-means++ seeding (2 + log K local trials,
         sklearn's _kmeans_plusplus) then Lloyd iterations until the squared centre shift is
-        <= tol * mean feature variance."""
+        <= tol * mean feature variance.  kmeans_backend='native': the same seeding and stop rule
+        through come_amd.kmeans.KMeans (the Lloyd iterations in libcome.so, the shift read every
+        fourth iteration)."""
         import torch
+        if self.kmeans_backend == 'native':
+            from .kmeans import KMeans
+            km = KMeans(self.n_components, n_init=1, max_iter=self.kmeans_max_iter,
+                        tol=self.kmeans_tol, distributed=self.distributed, group=self.group)
+            return km._fit_device(X, gen)._labels
         V, d = X.shape
         K = self.n_components
         rank, world = self._rank_world()
