@@ -16,8 +16,10 @@
                   graph_utils.build_deepwalk_corpus) on host threads.
   --workload kmeans  the k-means initialisation of the C4 GMM fit (1M rows, K=50, d=128): ms per
                   Lloyd iteration of the torch path and of the native kernels (come_amd.kmeans) from
-                  the same centres, both seedings, a full KMeans.fit, and the k-means share of a
-                  GaussianMixture fit with each kmeans_backend; roofline: X read once against HBM.
+                  the same centres, the torch seedings and the native one (kmeans_plusplus_native,
+                  and its pass over X alone against HBM), a full KMeans.fit with each seeding, and
+                  the k-means share of a GaussianMixture fit with each kmeans_backend /
+                  kmeans_seeding; roofline: X read once against HBM.
 Each prints one JSON line.  CPU baselines on a bounded sample: O1 the builder's Hogwild C
 restatement of train_o1 (oracle/come_oracle_mt.c; reported beside it as the reference-equivalent
 rate, restatement / its calibrated speed-up over the reference's GIL-bound Node2Vec.train,
@@ -26,6 +28,7 @@ oracle/oracle.py and sklearn predict_proba.  The reference itself never reaches 
 """
 import argparse
 import json
+import math
 import os
 import sys
 import threading
@@ -411,6 +414,20 @@ def kmeans_bench(args):
     seed_native_ms, C1 = wall(lambda: kmeans.kmeans_plusplus(X, xx, K, gens()))
     same_seeds = bool(torch.equal(C0, C1))
     C0 = C0.contiguous()
+    # the seeding in libcome.so (kmeans_plusplus_native): the whole seeding by the wall clock, and
+    # its pass over X (come_kmeans_pp_step: k_pp_step + k_pp_pots) alone by events
+    kmeans.kmeans_plusplus_native(X[:4096].contiguous(), K, gens())  # warm-up
+    seed_kernels_ms, _ = wall(lambda: kmeans.kmeans_plusplus_native(X, K, gens()))
+    trials = 2 + int(math.log(K))
+    pp_chunks, _ = kmeans.pp_plan(V, d, trials, kmeans._cus(dev))
+    pp_cand = torch.randint(0, V, (trials,), generator=gens(), device=dev).to(torch.int32)
+    pp_out = kmeans.pp_step(X, xx, pp_cand, pp_chunks)
+    _, ss = timed(lambda: kmeans.pp_step(X, xx, pp_cand, pp_chunks, out=pp_out), args.steps,
+                  args.warmup)
+    t_step = float(np.mean(ss))
+    log("seeding: torch %.1f ms, native estimator's torch chain %.1f ms, kernels %.1f ms; one "
+        "step kernel %.3f ms (%d candidates)" % (seed_torch_ms, seed_native_ms, seed_kernels_ms,
+                                                 t_step, trials))
 
     def torch_iter(C):  # gmm.py _kmeans_labels, one iteration
         dist_ = xx[:, None] - 2 * X @ C.t() + (C * C).sum(1)[None]
@@ -449,12 +466,15 @@ def kmeans_bench(args):
     log("torch %.3f ms / iteration, native %.3f ms (lloyd + reduce launches alone %.3f ms)" % (
         t_torch, t_native, t_kernel))
     fit_ms, km = wall(lambda: kmeans.KMeans(K, random_state=0).fit(X))
+    fit_pp_ms, km_pp = wall(lambda: kmeans.KMeans(K, random_state=0, seeding='native').fit(X))
     shares = {}
-    for backend in ("torch", "native"):
+    for name, backend, seeding in (("torch", "torch", "torch"), ("native", "native", "torch"),
+                                   ("native_seeding_native", "native", "native")):
         gmm.GaussianMixture(K, reg_covar=1e-5, max_iter=2, random_state=0, kmeans_max_iter=2,
-                            kmeans_backend=backend).fit(X)  # warm-up: library scratch, BLAS
+                            kmeans_backend=backend, kmeans_seeding=seeding).fit(X)  # warm-up:
+        # library scratch, BLAS
         m = gmm.GaussianMixture(K, reg_covar=1e-5, n_init=1, random_state=0,
-                                kmeans_backend=backend)
+                                kmeans_backend=backend, kmeans_seeding=seeding)
         spent = [0.0]
         inner = m._kmeans_labels
 
@@ -464,11 +484,11 @@ def kmeans_bench(args):
             return out
         m._kmeans_labels = timed_init
         total_ms, _ = wall(lambda: m.fit(X))
-        shares[backend] = {"fit_ms": total_ms, "kmeans_ms": spent[0],
-                           "kmeans_share": spent[0] / total_ms, "em_iterations": int(m.n_iter_),
-                           "lower_bound": float(m.lower_bound_)}
-        log("GaussianMixture fit, kmeans_backend=%s: %.0f ms, k-means %.0f ms" % (
-            backend, total_ms, spent[0]))
+        shares[name] = {"fit_ms": total_ms, "kmeans_ms": spent[0],
+                        "kmeans_share": spent[0] / total_ms, "em_iterations": int(m.n_iter_),
+                        "lower_bound": float(m.lower_bound_)}
+        log("GaussianMixture fit, kmeans_backend=%s, kmeans_seeding=%s: %.0f ms, k-means %.0f ms"
+            % (backend, seeding, total_ms, spent[0]))
     mfma_flops = 2.0 * 2 * V * 64 * d  # scores and one-hot sums, K padded to 64
     print(json.dumps({
         "metric": "k-means Lloyd iteration, %d rows K=%d d=%d" % (V, K, d),
@@ -483,8 +503,16 @@ def kmeans_bench(args):
                    "max_centre_difference_after_%d_iterations" % args.steps: centre_diff,
                    "seeding_torch_ms": seed_torch_ms, "seeding_native_ms": seed_native_ms,
                    "seedings_identical": same_seeds,
+                   "seeding_native_kernels_ms": seed_kernels_ms,
+                   "seeding_kernels_speedup_vs_native_ms": seed_native_ms / seed_kernels_ms,
+                   "seeding_trials": trials,
+                   "seeding_step_kernel_ms": t_step,
+                   "seeding_step_kernel_hbm_gbs": V * d * 4 / (t_step / 1e3) / 1e9,
+                   "seeding_step_kernel_hbm_frac": V * d * 4 / (t_step / 1e3) / 1e9 / HBM_PEAK_GBS,
                    "kmeans_fit_ms": fit_ms, "kmeans_fit_n_iter": int(km.n_iter_),
                    "kmeans_fit_seeding_share": seed_native_ms / fit_ms,
+                   "kmeans_fit_seeding_native_ms": fit_pp_ms,
+                   "kmeans_fit_seeding_native_n_iter": int(km_pp.n_iter_),
                    "gaussian_mixture_fit": shares},
         "roofline": {"bound": "hbm", "achieved": V * d * 4 / (t_kernel / 1e3) / 1e9,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s",

@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* ABI 5, additive (the version is unchanged: nothing that existed moved): come_kmeans_scratch,
+/* ABI 5, additive: come_kmeans_pp_scratch, come_kmeans_pp_step, come_kmeans_pp_pick and
+ * come_kmeans_pp_sample (the greedy k-means++ seeding of come_amd.kmeans).
+ * ABI 5, additive (the version is unchanged: nothing that existed moved): come_kmeans_scratch,
  * come_kmeans_lloyd, come_kmeans_assign and come_kmeans_update (k-means for the GMM init and
  * come_amd.kmeans.KMeans).
  * ABI 5 (this header): "gmm_cov_async" accepts 3 / 4 / 5.  Its default 4 now runs k_gmm_cov_fb3 at
@@ -222,6 +224,50 @@ int come_kmeans_assign(const float *x, int64_t V, int d, const float *centers, i
                        int32_t *labels_out, float *mindist_out, void *stream);
 int come_kmeans_update(float *centers, const double *sums, const int64_t *counts, int K, int d,
                        double *stats2, void *stream);
+
+/* ---- greedy k-means++ seeding (sklearn's _kmeans_plusplus with T local trials per step) ----
+ * One step: come_kmeans_pp_step on the T candidates, come_kmeans_pp_pick, come_kmeans_pp_sample
+ * for the next step's candidates.  Nothing is read by the host: the candidates, the choice and the
+ * potentials stay on the device.  x [V x d] device fp32, not necessarily 16-byte aligned;
+ * 1 <= V < 2^31, 1 <= d <= 512, 1 <= T <= 16.  No float atomics: every output is bit-identical
+ * from run to run.
+ *
+ * come_kmeans_pp_scratch (host): the row chunking for a device with `cus` compute units (<= 0:
+ * 256): chunks_out >= 1 with chunks * T * 8 <= 2 MB, and rows_per_chunk_out (a multiple of 32) with
+ * chunks * rows_per_chunk >= V > (chunks - 1) * rows_per_chunk.
+ *
+ * come_kmeans_pp_step: the one pass over x.  cand: device int32 [T], row indices of x.  closest:
+ * device fp32 [V], the squared distance to the nearest centre chosen so far, or NULL for +inf (the
+ * first centre).  dist_out [V x T] (fp32): dist_out[i][t] = min(closest[i], sum_j (x[i][j] -
+ * x[cand[t]][j])^2), the sum taken over the squared differences in fp32 (a candidate's own row
+ * gets exactly 0; nothing cancels, nothing is clamped).  ppot [chunks x T] (float64): the column
+ * sums of dist_out over each chunk's rows (chunk c = rows c R .. c R + R - 1, R = ceil(V / chunks)
+ * rounded up to a multiple of 32: with the planner's chunks, its rows_per_chunk; a chunk past the
+ * rows gets 0); pots_out [T] (float64): the sum of ppot's rows in chunk order.  A cand[t] outside
+ * [0, V) gives a column of +inf with potential +inf; nothing is read out of bounds.
+ *
+ * come_kmeans_pp_pick: best = argmin_t pots[t], ties to the lowest t, into best_out (device
+ * int32); closest_out[i] = dist[i][best]; cpot_out[c] = ppot[c][best]; pot_out = pots[best]
+ * (device float64).
+ *
+ * come_kmeans_pp_sample: u: device float64 [T], uniform draws in [0, 1).  With pot = the sum of
+ * cpot in chunk order and r = u[t] * pot, cand_out[t] (device int32) = the first row i with
+ * cum[i] >= r, clamped to V - 1 (a searchsorted), where cum is the float64 cumulative sum of
+ * closest: the chunk's prefix of cpot plus the running sum of the chunk's rows.  Whenever pot > 0
+ * and u[t] > 0 the row returned has closest > 0 (a chosen centre or a duplicate of one is never
+ * drawn again); pot == 0 returns row 0.  cpot and rows_per_chunk are those of the step that
+ * produced closest. */
+int come_kmeans_pp_scratch(int64_t V, int d, int T, int cus, int *chunks_out,
+                           int *rows_per_chunk_out);
+int come_kmeans_pp_step(const float *x, int64_t V, int d, const float *closest,
+                        const int32_t *cand, int T, int chunks, float *dist_out, double *ppot,
+                        double *pots_out, void *stream);
+int come_kmeans_pp_pick(const float *dist, int64_t V, int T, const double *ppot,
+                        const double *pots, int chunks, float *closest_out, double *cpot_out,
+                        int32_t *best_out, double *pot_out, void *stream);
+int come_kmeans_pp_sample(const float *closest, int64_t V, const double *cpot, int chunks,
+                          int rows_per_chunk, const double *u, int T, int32_t *cand_out,
+                          void *stream);
 
 /* ---- Random walks: the producer of train_o2's input (utils/graph_utils.py) ----
  * Graphs are CSR over node POSITIONS 0..V-1 in networkx order (see come_graph_from_edges):

@@ -32,7 +32,8 @@ SYMBOLS = ("come_abi_version", "come_last_error", "come_init", "come_exp_table",
            "come_delta_gather", "come_delta_scatter", "come_cpu_sgns_o2", "come_cpu_sgns_o1",
            "come_cpu_community_grad", "come_cpu_gmm_resp", "come_cpu_gmm_estep",
            "come_source_sha256", "come_kmeans_scratch", "come_kmeans_lloyd",
-           "come_kmeans_assign", "come_kmeans_update")
+           "come_kmeans_assign", "come_kmeans_update", "come_kmeans_pp_scratch",
+           "come_kmeans_pp_step", "come_kmeans_pp_pick", "come_kmeans_pp_sample")
 
 OPTION_FIELDS = ("o2_kernel", "o2_blocks_per_cu", "o2_waves_per_block",
                  "o2_static", "rows_per_wave", "o1_rows_per_wave",
@@ -109,6 +110,10 @@ def lib():
     L.come_kmeans_lloyd.argtypes = [P, i64, i32, P, i32, i32, P, P, P, P, P, P, P]
     L.come_kmeans_assign.argtypes = [P, i64, i32, P, i32, P, P, P]
     L.come_kmeans_update.argtypes = [P, P, P, i32, i32, P, P]
+    L.come_kmeans_pp_scratch.argtypes = [i64, i32, i32, i32, P, P]
+    L.come_kmeans_pp_step.argtypes = [P, i64, i32, P, P, i32, i32, P, P, P, P]
+    L.come_kmeans_pp_pick.argtypes = [P, i64, i32, P, P, i32, P, P, P, P, P]
+    L.come_kmeans_pp_sample.argtypes = [P, i64, P, i32, i32, P, i32, P, P]
     L.come_make_table.argtypes = [P, i64, P, u64, f64]
     L.come_count_o2_pairs.argtypes = [P, i64, i32, i32]
     L.come_count_o2_pairs.restype = i64

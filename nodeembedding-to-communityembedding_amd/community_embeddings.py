@@ -1,7 +1,8 @@
 """Community embedding trainer -- reference: ADSCModel/community_embeddings.py.
 
-``Community2Vec(model, lr, reg_covar, gmm_backend="gpu", kmeans_backend='torch')``
-(``kmeans_backend='native'``: the mixture's k-means initialisation on come_amd.kmeans):
+``Community2Vec(model, lr, reg_covar, gmm_backend="gpu", kmeans_backend='torch',
+kmeans_seeding='torch')`` (``kmeans_backend='native'``: the mixture's k-means initialisation on
+come_amd.kmeans; ``kmeans_seeding='native'``: its k-means++ seeding in libcome.so too):
   * ``fit(model)`` (:20-37): fits a GaussianMixture(n_components=k, covariance_type='full',
     n_init=10, reg_covar) -- by default the GPU EM of come_amd.gmm (MFMA E-step and M-step
     kernels, k-means init; unseeded like the reference's: the init draws its seed from the global
@@ -70,7 +71,7 @@ def community_grad(x, pi, mu, inv_cov, beta, lr, iters):
 
 class Community2Vec(object):
     def __init__(self, model, lr, reg_covar=0, gmm_backend="gpu", distributed=False,
-                 group=None, kmeans_backend='torch'):
+                 group=None, kmeans_backend='torch', kmeans_seeding='torch'):
         self.lr = lr
         self.gmm_backend = gmm_backend
         self.distributed = bool(distributed)
@@ -80,7 +81,8 @@ class Community2Vec(object):
             self.g_mixture = GaussianMixture(n_components=model.k, reg_covar=reg_covar,
                                              covariance_type='full', n_init=10,
                                              distributed=distributed, group=group,
-                                             kmeans_backend=kmeans_backend)
+                                             kmeans_backend=kmeans_backend,
+                                             kmeans_seeding=kmeans_seeding)
         elif gmm_backend == "sklearn":
             if distributed:
                 raise ValueError("distributed=True needs gmm_backend='gpu'")

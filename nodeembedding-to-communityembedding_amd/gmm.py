@@ -168,9 +168,13 @@ class GaussianMixture(object):
                  max_iter=100, n_init=1, init_params='kmeans', weights_init=None,
                  means_init=None, precisions_init=None, random_state=None, kmeans_max_iter=300,
                  kmeans_tol=1e-4, device=None, distributed=False, group=None,
-                 kmeans_backend='torch'):
+                 kmeans_backend='torch', kmeans_seeding='torch'):
         if kmeans_backend not in ('torch', 'native'):
             raise ValueError("kmeans_backend must be 'torch' or 'native'")
+        if kmeans_seeding not in ('torch', 'native'):
+            raise ValueError("kmeans_seeding must be 'torch' or 'native'")
+        if kmeans_seeding == 'native' and kmeans_backend != 'native':
+            raise ValueError("kmeans_seeding='native' needs kmeans_backend='native'")
         if covariance_type != 'full':
             raise NotImplementedError("only covariance_type='full' (the reference's) is "
                                       "implemented")
@@ -193,6 +197,7 @@ class GaussianMixture(object):
         self.distributed = bool(distributed)
         self.group = group
         self.kmeans_backend = kmeans_backend
+        self.kmeans_seeding = kmeans_seeding
 
     def _rank_world(self):
         return world_of(self.group) if self.distributed else (0, 1)
@@ -318,12 +323,14 @@ class GaussianMixture(object):
         sklearn's _kmeans_plusplus) then Lloyd iterations until the squared centre shift is
         <= tol * mean feature variance.  kmeans_backend='native': the same seeding and stop rule
         through come_amd.kmeans.KMeans (the Lloyd iterations in libcome.so, the shift read every
-        fourth iteration)."""
+        fourth iteration); with kmeans_seeding='native' the seeding runs in libcome.so too
+        (come_amd.kmeans.kmeans_plusplus_native: the same distribution, another random stream)."""
         import torch
         if self.kmeans_backend == 'native':
             from .kmeans import KMeans
             km = KMeans(self.n_components, n_init=1, max_iter=self.kmeans_max_iter,
-                        tol=self.kmeans_tol, distributed=self.distributed, group=self.group)
+                        tol=self.kmeans_tol, distributed=self.distributed, group=self.group,
+                        seeding=self.kmeans_seeding)
             return km._fit_device(X, gen)._labels
         V, d = X.shape
         K = self.n_components

@@ -8,6 +8,11 @@ once, no [V, K] matrix, no float atomics, bit-identical from run to run), and co
 (centres in place, the squared shift into a device double).  The host reads that shift only every
 ``check_every`` iterations.
 
+The greedy k-means++ seeding in front of them is a chain of torch ops (``kmeans_plusplus``, the
+default) or, with ``seeding='native'``, three more entry points per step
+(``kmeans_plusplus_native``: come_kmeans_pp_sample, come_kmeans_pp_step, come_kmeans_pp_pick; one
+read of X per step, nothing read back to the host; the same distribution, another random stream).
+
 ``KMeans`` keeps sklearn's surface for what is used here: ``n_clusters``, ``init`` ('k-means++' or
 an array [K, d]), ``n_init``, ``max_iter``, ``tol`` (scaled by the mean feature variance, sklearn's
 _tolerance), ``random_state``; ``fit`` / ``fit_predict`` / ``predict``; ``cluster_centers_``,
@@ -120,11 +125,145 @@ def kmeans_plusplus(X, xx, K, gen):
     return torch.stack(centers)
 
 
+def pp_plan(V, d, T, cus=0):
+    """(chunks, rows_per_chunk) of the native seeding's pass over V rows with T candidates on a
+    device with `cus` compute units (come_kmeans_pp_scratch): chunks * T * 8 bytes <= 2 MB."""
+    import ctypes
+    chunks, rows = ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.lib().come_kmeans_pp_scratch(int(V), int(d), int(T), int(cus), ctypes.byref(chunks),
+                                            ctypes.byref(rows)), "come_kmeans_pp_scratch")
+    return chunks.value, rows.value
+
+
+def pp_step(X, closest, cand, chunks, out=None):
+    """The seeding's one pass over X for the candidates `cand` (device int32 [T], rows of X):
+    (dist fp32 [V, T] = min(closest, squared distance to each candidate), ppot float64 [chunks, T]
+    its per-chunk column sums, pots float64 [T] their totals).  closest: device fp32 [V] or None
+    (+inf).  `out` = (dist, ppot, pots) to write into."""
+    import torch
+    V, d = X.shape
+    T = cand.shape[0]
+    if out is None:
+        out = (torch.empty((V, T), dtype=torch.float32, device=X.device),
+               torch.empty((chunks, T), dtype=torch.float64, device=X.device),
+               torch.empty((T,), dtype=torch.float64, device=X.device))
+    dist, ppot, pots = out
+    check(_lib.lib().come_kmeans_pp_step(ptr(X), V, d, None if closest is None else ptr(closest),
+                                         ptr(cand), T, chunks, ptr(dist), ptr(ppot), ptr(pots),
+                                         stream_handle(X.device)), "come_kmeans_pp_step")
+    return dist, ppot, pots
+
+
+def pp_pick(dist, ppot, pots, out=None):
+    """The best candidate of a step: (closest fp32 [V] = its column of dist, cpot float64 [chunks]
+    = its column of ppot, best int32 [1] = argmin pots with ties to the lowest index, pot float64
+    [1] = pots[best]), all on the device.  `out` = (closest, cpot, best, pot) to write into."""
+    import torch
+    V, T = dist.shape
+    chunks = ppot.shape[0]
+    if out is None:
+        out = (torch.empty((V,), dtype=torch.float32, device=dist.device),
+               torch.empty((chunks,), dtype=torch.float64, device=dist.device),
+               torch.empty((1,), dtype=torch.int32, device=dist.device),
+               torch.empty((1,), dtype=torch.float64, device=dist.device))
+    closest, cpot, best, pot = out
+    check(_lib.lib().come_kmeans_pp_pick(ptr(dist), V, T, ptr(ppot), ptr(pots), chunks,
+                                         ptr(closest), ptr(cpot), ptr(best), ptr(pot),
+                                         stream_handle(dist.device)), "come_kmeans_pp_pick")
+    return closest, cpot, best, pot
+
+
+def pp_sample(closest, cpot, rows_per_chunk, u, out=None):
+    """Rows drawn with probability proportional to `closest`: for each u[t] (device float64 in
+    [0, 1)) the first row whose float64 cumulative sum of closest reaches u[t] * its total; device
+    int32 [T].  cpot / rows_per_chunk: the chunk sums of closest (pp_step, pp_pick) and pp_plan's
+    rows per chunk.  A row with closest == 0 is never returned for u > 0 unless all are 0."""
+    import torch
+    V = closest.shape[0]
+    T = u.shape[0]
+    if out is None:
+        out = torch.empty((T,), dtype=torch.int32, device=closest.device)
+    check(_lib.lib().come_kmeans_pp_sample(ptr(closest), V, ptr(cpot), cpot.shape[0],
+                                           int(rows_per_chunk), ptr(u), T, ptr(out),
+                                           stream_handle(closest.device)), "come_kmeans_pp_sample")
+    return out
+
+
+def kmeans_plusplus_native(X, K, gen, first=None, u=None, return_trace=False):
+    """sklearn's greedy k-means++ seeding (2 + log K local trials) on the kernels of libcome.so:
+    [K, d] centres, rows of X.  Each of the K - 1 steps is one read of X (come_kmeans_pp_step: the
+    candidates' distances summed from squared differences, no [V, d] x [d, trials] product), the
+    choice of the candidate of lowest potential (come_kmeans_pp_pick) and the draw of the next
+    candidates from the float64 cumulative sum (come_kmeans_pp_sample); nothing is read back to the
+    host and all scratch is allocated before the loop.
+
+    The distribution is that of ``kmeans_plusplus``; the random stream is not: the first centre is
+    one ``torch.randint`` draw from `gen` (or `first`, device int64 [1]) and all uniforms are one
+    ``torch.rand`` [K - 1, trials] float64 from `gen` (or `u`), drawn up front, not once per step,
+    and the distances carry another fp32 rounding.  The same seed therefore gives other centres
+    than the torch seeding.
+
+    return_trace=True: (centres, chosen int64 [K], candidates int32 [K - 1, trials], potentials
+    float64 [K - 1, trials], best int32 [K - 1]), all on the device."""
+    import torch
+    V, d = X.shape
+    if V < K:
+        raise ValueError("k-means++ seeding needs >= n_clusters rows on rank 0")
+    if X.dtype != torch.float32 or not X.is_contiguous():
+        raise ValueError("X must be a contiguous float32 array")
+    dev = X.device
+    trials = 2 + int(math.log(K))
+    if first is None:
+        first = torch.randint(0, V, (1,), generator=gen, device=dev)
+    if u is None:
+        u = torch.rand((K - 1, trials), generator=gen, device=dev, dtype=torch.float64)
+    if tuple(u.shape) != (K - 1, trials) or u.dtype != torch.float64 or not u.is_contiguous():
+        raise ValueError("u must be a contiguous float64 array [%d, %d]" % (K - 1, trials))
+    chunks, rows = pp_plan(V, d, trials, _cus(dev))
+    closest = torch.empty((V,), dtype=torch.float32, device=dev)
+    cpot = torch.empty((chunks,), dtype=torch.float64, device=dev)
+    pot = torch.empty((1,), dtype=torch.float64, device=dev)
+    step_out = (torch.empty((V, trials), dtype=torch.float32, device=dev),
+                torch.empty((chunks, trials), dtype=torch.float64, device=dev))
+    cands = torch.empty((max(K - 1, 1), trials), dtype=torch.int32, device=dev)
+    pots = torch.empty((max(K - 1, 1), trials), dtype=torch.float64, device=dev)
+    best = torch.empty((max(K - 1, 1),), dtype=torch.int32, device=dev)
+    # the first centre: one candidate against +inf writes closest and its chunk sums directly
+    pp_step(X, None, first.to(torch.int32), chunks, out=(closest.view(V, 1), cpot.view(chunks, 1),
+                                                         pot))
+    # pp_sample, pp_step and pp_pick on raw addresses: K - 1 rounds of three calls, with no tensor
+    # view or stream lookup between them (the host's share of a round would otherwise exceed the
+    # kernels')
+    L, stream = _lib.lib(), stream_handle(dev)
+    a_x, a_closest, a_cpot, a_pot, a_dist, a_ppot, a_u, a_cands, a_pots, a_best = (
+        t.data_ptr() for t in (X, closest, cpot, pot, step_out[0], step_out[1], u, cands, pots,
+                               best))
+    for k in range(K - 1):
+        a_c, a_p = a_cands + 4 * trials * k, a_pots + 8 * trials * k
+        rc = L.come_kmeans_pp_sample(a_closest, V, a_cpot, chunks, rows, a_u + 8 * trials * k,
+                                     trials, a_c, stream)
+        rc = rc or L.come_kmeans_pp_step(a_x, V, d, a_closest, a_c, trials, chunks, a_dist,
+                                         a_ppot, a_p, stream)
+        rc = rc or L.come_kmeans_pp_pick(a_dist, V, trials, a_ppot, a_p, chunks, a_closest,
+                                         a_cpot, a_best + 4 * k, a_pot, stream)
+        check(rc, "come_kmeans_pp_sample / _step / _pick")
+    cands, pots, best = cands[:K - 1], pots[:K - 1], best[:K - 1]
+    chosen = torch.cat([first.long(), cands.long().gather(1, best.long()[:, None])[:, 0]])
+    centers = X.index_select(0, chosen)
+    if return_trace:
+        return centers, chosen, cands, pots, best
+    return centers
+
+
 class KMeans(object):
     def __init__(self, n_clusters=8, init='k-means++', n_init=1, max_iter=300, tol=1e-4,
-                 random_state=None, check_every=4, device=None, distributed=False, group=None):
+                 random_state=None, check_every=4, device=None, distributed=False, group=None,
+                 seeding='torch'):
         if isinstance(init, str) and init != 'k-means++':
             raise ValueError("init must be 'k-means++' or an array [n_clusters, d]")
+        if seeding not in ('torch', 'native'):
+            raise ValueError("seeding must be 'torch' or 'native'")
+        self.seeding = seeding
         if int(check_every) < 1:
             raise ValueError("check_every must be >= 1")
         self.n_clusters = int(n_clusters)
@@ -184,7 +323,9 @@ class KMeans(object):
                 raise ValueError("init must have shape (%d, %d)" % (K, d))
             return C.contiguous().clone()
         rank, world = self._rank_world()
-        if rank == 0:
+        if rank == 0 and self.seeding == 'native':
+            C = kmeans_plusplus_native(X, K, gen).contiguous()
+        elif rank == 0:
             C = kmeans_plusplus(X, xx, K, gen).contiguous()
         else:
             C = torch.empty((K, d), dtype=torch.float32, device=X.device)
@@ -204,7 +345,7 @@ class KMeans(object):
                              "d = 64, 128 and d > 128)")
         world = self._rank_world()[1]
         tol = self._tolerance(X)
-        xx = (X * X).sum(1) if isinstance(self.init, str) else None
+        xx = (X * X).sum(1) if isinstance(self.init, str) and self.seeding == 'torch' else None
         best = None
         for _ in range(self.n_init if isinstance(self.init, str) else 1):
             C = self._seed(X, xx, gen)
