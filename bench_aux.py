@@ -20,6 +20,13 @@
                   and its pass over X alone against HBM), a full KMeans.fit with each seeding, and
                   the k-means share of a GaussianMixture fit with each kmeans_backend /
                   kmeans_seeding; roofline: X read once against HBM.
+  --workload community_loss  the community objective at C4's shape (1M rows, K=50, d=128): ms per
+                  pass of come_community_loss (pack + kernel + reduction) and of come_gmm_estep on
+                  the same operands in the same run (the loss runs the E-step's MFMA stream and
+                  reads V x K x 4 B of pi where the E-step writes and re-reads as much resp), and of
+                  community_embeddings.community_loss end to end (factors derived, total read back).
+                  Reference: the numpy / scipy formula (multivariate_normal.logpdf weighted by pi)
+                  on a row subset, scaled to V.
 Each prints one JSON line.  CPU baselines on a bounded sample: O1 the builder's Hogwild C
 restatement of train_o1 (oracle/come_oracle_mt.c; reported beside it as the reference-equivalent
 rate, restatement / its calibrated speed-up over the reference's GIL-bound Node2Vec.train,
@@ -522,6 +529,77 @@ def kmeans_bench(args):
         "cpu_baseline": None}))
 
 
+def community_loss_bench(args):
+    import torch
+    from come_amd import _lib
+    from come_amd import community_embeddings as ce
+    from come_amd import gmm
+    dev = torch.device("cuda", 0)
+    V, K, d = args.nodes, args.k, args.dim
+    rng = np.random.RandomState(2)  # c4's operands
+    x = torch.from_numpy(rng.standard_normal((V, d)).astype(np.float32)).to(dev)
+    A = rng.standard_normal((K, d, d)) / np.sqrt(d)
+    cov = (np.einsum("kij,klj->kil", A, A) + np.eye(d)[None] * 0.5).astype(np.float32)
+    mu = (rng.standard_normal((K, d)) * 0.5).astype(np.float32)
+    pi_h = np.random.RandomState(3).dirichlet(np.ones(K), V).astype(np.float32)
+    pi = torch.from_numpy(pi_h).to(dev)
+    mu_t, cov_t = torch.from_numpy(mu).to(dev), torch.from_numpy(cov).to(dev)
+    pc, mp, ln = ce.community_loss_params(mu_t, cov_t)
+    total = torch.zeros(1, dtype=torch.float64, device=dev)
+    L, ptr, stream = _lib.lib(), _lib.ptr, _lib.stream_handle(dev)
+
+    def loss_pass():
+        _lib.check(L.come_community_loss(ptr(x), V, d, ptr(pi), ptr(pc), ptr(mp), ptr(ln), K, None,
+                                         ptr(total), stream), "come_community_loss")
+    _, ks_l = timed(loss_pass, args.steps, args.warmup)
+    _, ks_e = timed(lambda: gmm.estep(x, pc, mp, ln), args.steps, args.warmup)
+    _, ks_l2 = timed(loss_pass, args.steps, args.warmup)  # again after the E-step: same-run spread
+    _, ks_p = timed(lambda: ce.community_loss(x, pi, mu_t, cov_t), args.steps, args.warmup)
+    tl, te, tl2, tp = (float(np.mean(k)) for k in (ks_l, ks_e, ks_l2, ks_p))
+    value = ce.community_loss(x, pi, mu_t, cov_t)
+    flops = 2.0 * V * K * d * d
+    # the MFMA blocks executed on the upper factors (k_comm_loss_b16 as k_gmm_resp_b16: 16-wide
+    # column tiles x 32-feature steps, 20 of 32 at d = 128, 6 of 8 at d = 64); six bf16 part
+    # products per multiply-add, so the ceiling is the bf16 MFMA peak / 6
+    tri = {128: 20 / 32, 64: 6 / 8}.get(d, 1.0)
+    cpu = None
+    if not args.no_cpu_baseline:
+        from scipy.stats import multivariate_normal
+        S = min(V, 2000)
+        xs, ps = x[:S].cpu().numpy().astype(np.float64), pi_h[:S].astype(np.float64)
+        t0 = time.time()
+        sub = sum((ps[:, k] * multivariate_normal(mu[k].astype(np.float64),
+                                                  cov[k].astype(np.float64)).logpdf(xs)).sum()
+                  for k in range(K))
+        cel = time.time() - t0
+        sub_gpu = ce.community_loss(x[:S], pi[:S], mu_t, cov_t)
+        cpu = {"value": cel * V / S * 1e3, "unit": "ms per pass (scaled)", "kind": "reference",
+               "blas_threads": blas_threads(), "subset_rows": S,
+               "sample": "sum_k pi[:, k] * scipy.stats.multivariate_normal(mu_k, cov_k).logpdf(x) "
+                         "in float64 on %d of the %d rows: %.3f s, scaled by V / %d (the K "
+                         "factorisations are counted once per subset, so the scaled figure "
+                         "overstates them)" % (S, V, cel, S),
+               "subset_total_float64": sub, "subset_total_gpu": sub_gpu}
+    print(json.dumps({
+        "metric": "community loss, ms per pass, V=%d K=%d d=%d" % (V, K, d),
+        "value": tl, "unit": "ms", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "higher_is_better": False, "dtype": "f32 (bf16-part MFMA at d = 64, 128)",
+        "data": "synthetic (c4's operands, seed 2 / 3)",
+        "config": {"workload": "come_community_loss on %d rows, K=%d, d=%d (row_out = NULL)"
+                               % (V, K, d)},
+        "loss_ms": tl, "loss_ms_min": float(np.min(ks_l)), "loss_ms_second_timing": tl2,
+        "estep_ms": te, "estep_ms_min": float(np.min(ks_e)), "loss_over_estep": tl / te,
+        "python_community_loss_ms": tp, "total": value,
+        "roofline": {"bound": "mfma" if tri < 1.0 else "valu",
+                     "achieved": tri * flops / (tl / 1e3) / 1e12,
+                     "peak": BF16_MFMA_PEAK_TFLOPS / 6, "unit": "TFLOP/s (executed)",
+                     "frac": tri * flops / (tl / 1e3) / 1e12 / (BF16_MFMA_PEAK_TFLOPS / 6),
+                     "executed_block_fraction": tri,
+                     "dense_equivalent_tflops": flops / (tl / 1e3) / 1e12,
+                     "avg_kernel_ms": tl},
+        "cpu_baseline": cpu}))
+
+
 def blas_threads():
     """Threads of the BLAS pool numpy / scipy / sklearn run on in this process (threadpoolctl),
     None if it cannot tell."""
@@ -535,7 +613,7 @@ def blas_threads():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["c2", "c4", "walks", "kmeans"], required=True)
+    ap.add_argument("--workload", choices=["c2", "c4", "walks", "kmeans", "community_loss"], required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dim", type=int, default=128)
@@ -564,7 +642,8 @@ def main():
         for kv in args.opt:
             k, v = kv.split("=")
             _lib.set_option(k, int(v))
-    {"c2": c2, "c4": c4, "walks": walks, "kmeans": kmeans_bench}[args.workload](args)
+    {"c2": c2, "c4": c4, "walks": walks, "kmeans": kmeans_bench,
+     "community_loss": community_loss_bench}[args.workload](args)
 
 
 if __name__ == "__main__":

@@ -149,6 +149,26 @@ int come_community_grad(float *x, int64_t V, int d, const float *pi, const float
                         const float *inv_cov, int K, float beta, float lr, int iters,
                         void *stream);
 
+/* ---- Community loss: the objective come_community_grad descends, what Community2Vec.loss
+ * (community_embeddings.py:40-59) is meant to compute ----
+ *   row_i = sum_k pi[i,k] * (log_norm[k] - |x_i prec_chol[k] - mu_prec[k]|^2 / 2),  total = sum_i row_i
+ * i.e. sum_k pi[i,k] log N(x_i; mu_k, Sigma_k) when prec_chol[k] is the precision Cholesky factor
+ * of Sigma_k, mu_prec[k] = mu_k @ prec_chol[k] and log_norm[k] = log det(prec_chol[k]) - d/2
+ * log(2 pi) -- come_gmm_estep's operands with NO mixture weight in log_norm.  x [V x d], pi
+ * [V x K] (used as given: rows need not sum to 1), prec_chol [K x d x d], mu_prec [K x d],
+ * log_norm [K] (all device fp32); row_out [V] device fp32 or NULL; loss_out one device double
+ * (the rows summed in float64).  1 <= d <= 512, 1 <= K <= 4096 for every d.
+ * prec_chol MUST hold upper-triangular factors with zeros below the diagonal (what come_gmm_params
+ * writes): the kernels for d = 64, 128 never read most of the lower triangle and there is no
+ * check and no fallback for a lower or dense factor (unlike come_gmm_estep).  d = 64, 128 with
+ * 16-byte aligned x, prec_chol and mu_prec run come_gmm_estep's bf16-part MFMA stream, anything
+ * else a VALU kernel.  No float or double atomics: row_out and loss_out are bit-identical from run
+ * to run, and loss_out does not depend on whether row_out is given.  V = 0 is a no-op returning 0
+ * (loss_out is not written).  Asynchronous on `stream`. */
+int come_community_loss(const float *x, int64_t V, int d, const float *pi, const float *prec_chol,
+                        const float *mu_prec, const float *log_norm, int K, float *row_out,
+                        double *loss_out, void *stream);
+
 /* ---- GMM responsibilities: replaces GaussianMixture.predict_proba (community_embeddings.py:37)
  * for covariance_type='full'.  prec_chol [K x d x d] (precision Cholesky factors, sklearn
  * layout), mu_prec [K x d] = mu_k @ prec_chol_k, log_norm [K] = log w_k + log det(prec_chol_k)
@@ -489,7 +509,10 @@ int come_sgns_o1_ex(float *node, int64_t V, int d, const int32_t *edges, int64_t
  *                          order (= workers=1), bit-identical to come_sgns_o2 / _o1 sequential
  *                          mode (the same WAVE64 dot order).
  *  come_cpu_community_grad community_embeddings.py:61-78, k_community_grad's arithmetic order.
- *  come_cpu_gmm_resp / _estep  community_embeddings.py:37 predict_proba; _estep adds lse_out. */
+ *  come_cpu_gmm_resp / _estep  community_embeddings.py:37 predict_proba; _estep adds lse_out.
+ *  come_cpu_community_loss come_community_loss in float64 arithmetic (row_out [V] fp32 or NULL,
+ *                          loss_out one host double); the total is summed per thread block of rows,
+ *                          so it is reproducible for a given `threads`. */
 int come_cpu_sgns_o2(float *node, float *ctx, int64_t V, int d, const int32_t *walks, int64_t P,
                      int L, const uint64_t *seeds, int window, int negative, const uint32_t *table,
                      uint64_t T, float lr, float alpha, int mode, int threads, int64_t *pairs_out);
@@ -505,6 +528,9 @@ int come_cpu_gmm_resp(const float *x, int64_t V, int d, const float *prec_chol,
 int come_cpu_gmm_estep(const float *x, int64_t V, int d, const float *prec_chol,
                        const float *mu_prec, const float *log_norm, int K, float *resp_out,
                        float *lse_out, int threads);
+int come_cpu_community_loss(const float *x, int64_t V, int d, const float *pi,
+                            const float *prec_chol, const float *mu_prec, const float *log_norm,
+                            int K, float *row_out, double *loss_out, int threads);
 
 /* ---- Host helpers ---- */
 

@@ -14,6 +14,9 @@ come_amd.kmeans; ``kmeans_seeding='native'``: its k-means++ seeding in libcome.s
     x -= lr * clip((beta/K) sum_k pi_ik inv_cov_k (x_i - mu_k), +-5), ``iter`` times, on the GPU
     (come_community_grad).  Every row's gradient depends only on that row (:65 snapshot), so rows
     outside ``nodes`` are left untouched by gathering/scattering the selected rows.
+  * ``loss(nodes, model, beta, chunksize)`` (:40-59): the objective ``train`` descends,
+    (beta / K) |sum_i sum_k pi_ik log N(x_i; mu_k, Sigma_k)| over the listed nodes, on the GPU
+    (come_community_loss; ``community_loss`` is the signed total for tensors).
   * ``responsibilities(model)``: predict_proba of the fitted mixture on the current embedding.
 
 Multi-GPU (``distributed=True``): every rank holds a full replica of
@@ -22,7 +25,8 @@ node_embedding (as after the SGNS phase) and owns the contiguous row block
 sufficient statistics (come_amd.gmm, distributed=True) and all-gathers the responsibilities;
 ``train`` applies the community gradient to the rank's block only (rows are independent, :65) and
 all-gathers the updated rows once per call (after all ``iter`` steps), so the replicas agree
-bit for bit with a single-GPU run.  No other exchange is needed.
+bit for bit with a single-GPU run.  ``loss`` evaluates the rank's block and all-reduces the float64
+totals (as GaussianMixture.score).  No other exchange is needed.
 """
 import logging as log
 
@@ -30,7 +34,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr, stream_handle
-from .distributed import all_gather_rows, shard_range, world_of
+from .distributed import all_gather_rows, all_reduce_sum, shard_range, world_of
 
 
 def gmm_resp(x, prec_chol, mu_prec, log_norm):
@@ -67,6 +71,60 @@ def community_grad(x, pi, mu, inv_cov, beta, lr, iters):
                                         float(beta), float(lr), int(iters),
                                         stream_handle(x.device))
     check(rc, "come_community_grad")
+
+
+def community_loss_params(mu, cov):
+    """What come_community_loss consumes, derived in float64 on the device and handed over as
+    fp32: (prec_chol, mu_prec, log_norm) with prec_chol[k] = P_k, the upper precision Cholesky
+    factor of cov[k].double() (zeros below the diagonal), mu_prec[k] = mu_k P_k and log_norm[k] =
+    c_k = sum(log diag P_k) - d/2 log(2 pi) (no mixture weight).  A covariance that is not positive
+    definite raises ValueError, as scipy's multivariate_normal does."""
+    import math
+
+    import torch
+    K, d = mu.shape
+    mu64, cov64 = mu.double().contiguous(), cov.double().contiguous()
+    if d <= 128:
+        # come_gmm_params with unit nk and weights and no regularisation: one launch
+        from . import gmm
+        one = torch.ones(K, dtype=torch.float64, device=mu.device)
+        _, _, e_pc, e_mp, e_ln, info = gmm.params(cov64, one, mu64, one, 0.0)
+    else:  # the torch path of GaussianMixture._set_params
+        chol, info = torch.linalg.cholesky_ex(cov64)
+        chol = torch.where(info.view(K, 1, 1) != 0, torch.eye(d, dtype=torch.float64,
+                                                                device=mu.device), chol)
+        eye = torch.eye(d, dtype=torch.float64, device=mu.device).expand_as(chol)
+        pc = torch.triu(torch.linalg.solve_triangular(chol, eye, upper=False).transpose(-1, -2))
+        log_det = torch.log(torch.diagonal(pc, dim1=-2, dim2=-1)).sum(-1)
+        e_pc = pc.float().contiguous()
+        e_mp = torch.einsum("kd,kde->ke", mu64, pc).float().contiguous()
+        e_ln = (log_det - 0.5 * d * math.log(2 * math.pi)).float().contiguous()
+    if bool((info != 0).any()):
+        raise ValueError("community_loss: covariance of component %d is not positive definite"
+                         % int(torch.nonzero(info)[0]))
+    return e_pc, e_mp, e_ln
+
+
+def community_loss(x, pi, mu, cov, return_rows=False):
+    """The signed community objective sum_i sum_k pi[i, k] log N(x_i; mu[k], cov[k]) for device
+    fp32 x [V, d], pi [V, K] (used as given: rows need not sum to 1), mu [K, d], cov [K, d, d], as
+    a Python float (the rows summed in float64); ``(total, rows)`` with rows a device fp32 [V]
+    tensor when ``return_rows``.  No rows: 0.0."""
+    import torch
+    V, d = x.shape
+    K = mu.shape[0]
+    rows = torch.zeros((V,), dtype=torch.float32, device=x.device) if return_rows else None
+    if V == 0:
+        return (0.0, rows) if return_rows else 0.0
+    pc, mp, ln = community_loss_params(mu, cov)
+    x, pi = x.contiguous(), pi.contiguous()
+    total = torch.zeros((1,), dtype=torch.float64, device=x.device)
+    rc = _lib.lib().come_community_loss(ptr(x), V, d, ptr(pi), ptr(pc), ptr(mp), ptr(ln), K,
+                                        ptr(rows) if return_rows else None, ptr(total),
+                                        stream_handle(x.device))
+    check(rc, "come_community_loss")
+    total = float(total.item())
+    return (total, rows) if return_rows else total
 
 
 class Community2Vec(object):
@@ -124,6 +182,35 @@ class Community2Vec(object):
         pi = torch.empty((V, pc.shape[0]), dtype=torch.float32, device=x.device)
         pi[lo:hi] = gmm_resp(x[lo:hi], pc, mp, ln)
         return all_gather_rows(pi, self.group)
+
+    def loss(self, nodes, model, beta, chunksize=150):
+        """community_embeddings.py:40-59 as it is meant: O3 = (beta / K) |sum_i sum_k pi_ik
+        log N(x_i; mu_k, Sigma_k)| over the listed nodes (each listing of a node counts once, so
+        a node listed twice counts twice), the objective ``train`` descends.  Departs from two
+        defects of the reference, which cannot run as written: :48 calls ``model.vocab(x)`` (a
+        dict; ``train`` indexes it), and :57 overwrites its accumulator with each component's
+        term where it should add it.  ``chunksize`` is accepted for the reference's signature and
+        has no effect (the sum does not depend on the chunking).  Reads model.centroid,
+        model.covariance_mat, model.pi and model.node_embedding only.  Ids outside the vocabulary
+        raise KeyError, as in ``train``."""
+        import torch
+        ids = np.fromiter((int(n) for n in nodes), np.int64)
+        rows = model.rows_of(ids)
+        if (rows < 0).any():
+            raise KeyError(int(ids[np.argmax(rows < 0)]))
+        x, pi = model.node_embedding, model.pi
+        if not (len(rows) == model.vocab_size and (rows == np.arange(len(rows))).all()):
+            idx = torch.from_numpy(np.ascontiguousarray(rows, np.int64)).to(x.device)
+            x, pi = x.index_select(0, idx), pi.index_select(0, idx)
+        lo, hi = self._shard(len(rows))
+        total = 0.0
+        if hi > lo:  # a row block of a C-contiguous table is itself contiguous
+            total = community_loss(x[lo:hi], pi[lo:hi], model.centroid, model.covariance_mat)
+        if self.distributed and world_of(self.group)[1] > 1:
+            t = torch.tensor([total], dtype=torch.float64, device=x.device)
+            all_reduce_sum([t], self.group)
+            total = float(t[0])
+        return abs(total) * beta / model.k
 
     def train(self, nodes, model, beta, chunksize=150, iter=1):
         """community_embeddings.py:61-78.  The reference walks `nodes` in chunks of `chunksize`

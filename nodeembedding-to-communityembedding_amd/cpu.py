@@ -7,6 +7,7 @@ to them.
     sgns_o1(node, edges, seeds, negative, table, lr, mode, threads)                   -> pairs
     community_grad(x, pi, mu, inv_cov, beta, lr, iters, threads)    (community_embeddings.py:61-78)
     gmm_estep(x, prec_chol, mu_prec, log_norm, threads) -> (resp, lse)  (predict_proba, :37)
+    community_loss(x, pi, prec_chol, mu_prec, log_norm, threads) -> total   (what :40-59 means)
 
 Tables are updated in place (float32, C-contiguous, as the reference's numpy arrays).  ``mode``:
 MODE_HOGWILD = ``threads`` workers taking jobs of 150 walks / edges with lock-free updates, as the
@@ -110,3 +111,24 @@ def gmm_estep(x, prec_chol, mu_prec, log_norm, threads=None):
                                         ptr(log_norm), K, ptr(resp), ptr(lse),
                                         _threads(threads)), "come_cpu_gmm_estep")
     return resp, lse
+
+
+def community_loss(x, pi, prec_chol, mu_prec, log_norm, return_rows=False, threads=None):
+    """sum_i sum_k pi[i, k] (log_norm[k] - |x_i prec_chol[k] - mu_prec[k]|^2 / 2) in float64 (as
+    come_community_loss: prec_chol the UPPER precision Cholesky factors, mu_prec[k] = mu_k @
+    prec_chol[k], log_norm[k] = log det(prec_chol[k]) - d/2 log(2 pi), no mixture weight).  Returns
+    the signed total as a Python float, or (total, rows [V] float32) with ``return_rows``."""
+    for a, n in ((x, "x"), (pi, "pi"), (prec_chol, "prec_chol"), (mu_prec, "mu_prec"),
+                 (log_norm, "log_norm")):
+        _arr(a, np.float32, n)
+    V, d = x.shape
+    K = log_norm.shape[0]
+    assert pi.shape == (V, K) and prec_chol.shape == (K, d, d) and mu_prec.shape == (K, d)
+    rows = np.zeros(V, np.float32) if return_rows else None
+    total = ctypes.c_double(0.0)
+    check(_lib.lib().come_cpu_community_loss(ptr(x), V, d, ptr(pi), ptr(prec_chol), ptr(mu_prec),
+                                             ptr(log_norm), K,
+                                             ptr(rows) if return_rows else None,
+                                             ctypes.byref(total), _threads(threads)),
+          "come_cpu_community_loss")
+    return (total.value, rows) if return_rows else total.value

@@ -18,6 +18,8 @@
 //                            over the threads (each row's update reads only its own row).
 //   come_cpu_gmm_resp/_estep GaussianMixture.predict_proba (community_embeddings.py:37) and the
 //                            E-step's per-row log-sum-exp, rows split over the threads.
+//   come_cpu_community_loss  the community objective (what community_embeddings.py:40-59 means),
+//                            float64 arithmetic, one partial sum per thread's block of rows.
 // Each compute body is built twice, for AVX2+FMA and for the baseline ISA (explicit fmaf either
 // way, -ffp-contract=off: identical results), and the first call picks one from the CPU.
 #include <stdint.h>
@@ -337,6 +339,38 @@ HOT void resp_rows(const Resp &a, int64_t lo, int64_t hi) {
 COME_FMA_CLONE void resp_rows_fma(const Resp &a, int64_t lo, int64_t hi) { resp_rows(a, lo, hi); }
 void resp_rows_base(const Resp &a, int64_t lo, int64_t hi) { resp_rows(a, lo, hi); }
 
+struct Loss {
+    const float *x, *pi, *prec_chol, *mu_prec, *log_norm;
+    float *row_out;
+    int64_t V;
+    int d, K;
+};
+
+// come_community_loss in float64: y_c = sum_{j <= c} x_j P_k[j][c] - (mu_k P_k)_c (the factors are
+// upper-triangular by the entry's contract), row = sum_k pi_k (log_norm_k - 0.5 sum_c y_c^2);
+// returns the sum of the rows lo .. hi - 1 in row order.
+double loss_rows(const Loss &a, int64_t lo, int64_t hi) {
+    double total = 0.0;
+    for (int64_t r = lo; r < hi; ++r) {
+        const float *x = a.x + r * a.d;
+        double row = 0.0;
+        for (int k = 0; k < a.K; ++k) {
+            const float *P = a.prec_chol + (int64_t)k * a.d * a.d;
+            double sq = 0.0;
+            for (int c = 0; c < a.d; ++c) {
+                double y = 0.0;
+                for (int j = 0; j <= c; ++j) y += (double)x[j] * (double)P[(int64_t)j * a.d + c];
+                y -= (double)a.mu_prec[(int64_t)k * a.d + c];
+                sq += y * y;
+            }
+            row += (double)a.pi[r * a.K + k] * ((double)a.log_norm[k] - 0.5 * sq);
+        }
+        if (a.row_out) a.row_out[r] = (float)row;
+        total += row;
+    }
+    return total;
+}
+
 int check_threads(int threads) {
     if (threads < 1 || threads > kMaxThreads)
         return set_error(COME_E_INVALID, "threads must be in [1, %d]", kMaxThreads);
@@ -421,6 +455,29 @@ extern "C" int come_cpu_gmm_estep(const float *x, int64_t V, int d, const float 
     const Resp a{x, prec_chol, mu_prec, log_norm, resp_out, lse_out, V, d, K};
     auto fn = have_fma() ? resp_rows_fma : resp_rows_base;
     parallel_rows(V, threads, [&](int64_t lo, int64_t hi) { fn(a, lo, hi); });
+    return COME_OK;
+}
+
+extern "C" int come_cpu_community_loss(const float *x, int64_t V, int d, const float *pi,
+                                       const float *prec_chol, const float *mu_prec,
+                                       const float *log_norm, int K, float *row_out,
+                                       double *loss_out, int threads) {
+    if (V < 0 || d < 1 || d > kMaxDim || K < 1 || K > 4096)
+        return set_error(COME_E_INVALID, "community_loss: need V>=0, 1<=d<=%d, 1<=K<=4096",
+                         kMaxDim);
+    int rc = check_threads(threads);
+    if (rc) return rc;
+    if (V == 0) return COME_OK;
+    if (!x || !pi || !prec_chol || !mu_prec || !log_norm || !loss_out)
+        return set_error(COME_E_INVALID, "community_loss: null pointer");
+    const Loss a{x, pi, prec_chol, mu_prec, log_norm, row_out, V, d, K};
+    // one partial per block of rows (parallel_rows' split), added in block order
+    const int64_t per = threads <= 1 || V < 64 ? V : (V + threads - 1) / threads;
+    std::vector<double> part((size_t)((V + per - 1) / per), 0.0);
+    parallel_rows(V, threads, [&](int64_t lo, int64_t hi) { part[lo / per] = loss_rows(a, lo, hi); });
+    double total = 0.0;
+    for (double p : part) total += p;
+    *loss_out = total;
     return COME_OK;
 }
 
