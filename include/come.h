@@ -182,7 +182,9 @@ int come_gmm_resp(const float *x, int64_t V, int d, const float *prec_chol, cons
 /* ---- GMM EM fit (replaces GaussianMixture.fit, community_embeddings.py:27; sklearn
  * BaseMixture.fit_predict / _e_step / _m_step for covariance_type='full') ----
  * E-step: come_gmm_resp plus lse_out [V] = per-row log sum_k exp(log w_k + log N(x; mu_k, S_k))
- * (the mean of lse_out is sklearn's log_prob_norm / lower bound). */
+ * (the mean of lse_out is sklearn's log_prob_norm / lower bound).  log_norm[k] may be -inf (a
+ * component of weight zero): such a component gets responsibility exactly 0 and adds nothing to
+ * lse_out, as long as some component of the launch is finite. */
 int come_gmm_estep(const float *x, int64_t V, int d, const float *prec_chol, const float *mu_prec,
                    const float *log_norm, int K, float *resp_out, float *lse_out, void *stream);
 

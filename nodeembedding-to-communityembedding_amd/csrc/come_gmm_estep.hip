@@ -86,6 +86,17 @@ __global__ void __launch_bounds__(256) k_transpose_sq(const float *__restrict__ 
     for (int y = y0; y < 32; y += 8) dst[(int64_t)(tc * 32 + y) * D + tr * 32 + x] = t[x][y];
 }
 
+// online log-sum-exp step.  A term of -inf (log_norm_k = log 0: a component of weight zero) adds
+// nothing; while the running max is still -inf its exponent would be -inf - -inf = NaN.
+__device__ __forceinline__ void lse_push(float lp, float &run_max, float &run_sum) {
+    if (lp > run_max) {
+        run_sum = run_sum * expf(run_max - lp) + 1.0f;
+        run_max = lp;
+    } else if (lp != -INFINITY) {
+        run_sum += expf(lp - run_max);
+    }
+}
+
 // ---- E-step on v_mfma_f32_16x16x4_f32: the FULL body (k_gmm_resp16_full) ------------------
 //
 // Y^T = P_k^T X^T per 16 x 16 tile: A = P_k^T (lane: column c = ct*16 + lane%16, features
@@ -300,12 +311,7 @@ __device__ __forceinline__ void r16_body(const RespArgs &a, float *sm, int64_t b
         const float tot = (kg & 1) ? tot1 : tot0;
         const float lp = lnk - 0.5f * tot;
         if (owner) a.resp[my_row * a.K + k] = lp;
-        if (lp > run_max) {  // online log-sum-exp of the row's components so far
-            run_sum = run_sum * expf(run_max - lp) + 1.0f;
-            run_max = lp;
-        } else {
-            run_sum += expf(lp - run_max);
-        }
+        lse_push(lp, run_max, run_sum);  // the row's components so far
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // half 1 and mu_k P_k free; half 0 of P_{k+1} in LDS
         if (k + 1 < a.K) {
@@ -490,7 +496,6 @@ __device__ __forceinline__ float r16t_lp_of(float sq, const float *par) {
     return par[Resp16T<D>::PAR + 1] - 0.5f * reduce_stage<5>(reduce_stage<4>(sq));
 }
 
-// online log-sum-exp step
 // A row's responsibilities from its stored log-probabilities: the row's four lanes (group kg)
 // take components k = kg, kg + 4, ..., each lane's loads issued as a batch of up to 16 before any
 // exp or store (one memory round trip where one lane walking all K took K); the last component's
@@ -508,15 +513,6 @@ __device__ __forceinline__ void resp_normalize(float *lp, int K, float lp_last, 
             const int k = k0 + 4 * u;
             if (k < K) lp[k] = expf(v[u] - lse);
         }
-    }
-}
-
-__device__ __forceinline__ void lse_push(float lp, float &run_max, float &run_sum) {
-    if (lp > run_max) {
-        run_sum = run_sum * expf(run_max - lp) + 1.0f;
-        run_max = lp;
-    } else {
-        run_sum += expf(lp - run_max);
     }
 }
 

@@ -207,6 +207,31 @@ def test_gmm_estep_vs_float64(V, K, d):
     np.testing.assert_allclose(lse, logsumexp(lp, 1), rtol=2e-5, atol=2e-3)
 
 
+@pytest.mark.parametrize("zero", [(0,), (0, 1), (2,), (5,)])
+@pytest.mark.parametrize("d", [8, 64])
+def test_gmm_estep_zero_weight_components(d, zero):
+    """log_norm = -inf (the log of a weight 0) on some of K = 6 components: their responsibilities
+    are exactly 0.0, the others and lse are those of the mixture of the remaining components
+    (tests/test_gpu_component_counts.py runs the same case through every GPU kernel)."""
+    from scipy.special import logsumexp
+    V, K = 130, 6
+    rng = np.random.RandomState(d)
+    X = rng.standard_normal((V, d)).astype(np.float32)
+    P = (np.triu(rng.standard_normal((K, d, d)) / np.sqrt(d)) + 2 * np.eye(d)).astype(np.float32)
+    mp = np.matmul(rng.standard_normal((K, 1, d)) * 0.3, P)[:, 0].astype(np.float32)
+    ln = np.log(rng.dirichlet(np.ones(K))).astype(np.float32)
+    ln[list(zero)] = -np.inf
+    resp, lse = cpu.gmm_estep(X, P, mp, ln, threads=2)
+    keep = [k for k in range(K) if k not in zero]
+    Y = np.einsum("vd,kde->vke", X.astype(np.float64), P[keep].astype(np.float64)) - mp[keep][None]
+    lp = ln[keep].astype(np.float64)[None] - 0.5 * (Y ** 2).sum(-1)
+    ref_lse = logsumexp(lp, 1)
+    assert not np.isnan(resp).any() and not np.isnan(lse).any()
+    assert (resp[:, list(zero)] == 0.0).all()
+    np.testing.assert_allclose(resp[:, keep], np.exp(lp - ref_lse[:, None]), atol=2e-4)
+    np.testing.assert_allclose(lse, ref_lse, rtol=2e-5, atol=2e-3)
+
+
 def test_argument_validation():
     from come_amd._lib import ComeError, TABLE_PACKED
     table, node, ctx, walks, seeds = rand_case(50, 8, 2, 10, 0)
