@@ -227,6 +227,15 @@ __device__ inline bool sigmoid_ref(float f, float *sig) {
     return true;
 }
 
+// The same lookup from a copy of the table (the stream kernel's LDS copy: no scalar-memory round
+// trip per target).
+__device__ inline bool sigmoid_tab(const float *tab, float f, float *sig) {
+    if (f <= -(float)kMaxExp || f >= (float)kMaxExp) return false;
+    const int b = (int)(((double)f + 6.0) * 83.0);
+    *sig = tab[b];
+    return true;
+}
+
 // ---- batch of 64 negative draws held one per lane ------------------------------------------
 struct DrawBatch {
     uint32_t target;  // this lane's table value for draw (base + lane)
@@ -818,6 +827,17 @@ __global__ void __launch_bounds__(128) k_sgns_o2_ring(O2Args a) {
 // wavefronts' atomics it was loaded with), a cold row's copy is replaced by the stored value (what
 // a read after the store returns; on walks that share no row the launch is bit-identical to the
 // sequential order, tests/test_gpu_stream.py).
+// Two paths per pair.  On large tables nearly every pair is *plain*: its
+// context-table rows (center, n draws) are distinct rows of the table, none of them is a row of the
+// next pair (whose center may be the same), and the next pair has another input row.  One vector
+// test over `ids` (the two pairs' rows, one per lane) decides it; a plain pair then skips the
+// per-target bookkeeping that exists for aliases -- the range and == center tests, the scan for a
+// repeated negative, the compares that patch prefetched copies -- and takes its (1 + n) sigmoids in
+// one step across lanes from the LDS copy of the exp table.  Every other pair runs the serial
+// resolution.  The arithmetic (loads, fma order, stores, atomics) is the same on both paths.
+// What is wave-uniform per target lives in lanes, not in scalar registers: the dots / g_k (`fv`),
+// the rows and hot bits (`ids`); the draw batches and the walk's positions sit in LDS, read by
+// lane or by uniform address.
 // Wavefronts per SIMD the stream kernel is compiled for: the kernel is latency-bound (one pair of
 // loads in flight per wavefront), so at d <= 128, n <= 5 it is held to 64 VGPRs for 8 waves per
 // SIMD (a 32-byte spill): 108 vs 119 ms per C3 launch at the 7 waves 70 VGPRs would give
@@ -845,12 +865,25 @@ __global__ void __launch_bounds__(256)
     const int path_len = a.L < kMaxSentenceLen ? a.L : kMaxSentenceLen;  // pyx:480
     auto valid_row = [&](int r) { return r >= 0 && r < a.V; };
     constexpr uint32_t kHotBit = 0x80000000u;
+    // the exp table in LDS, staged once per workgroup (4,000 bytes): a lookup is one ds_read
+    // instead of two dependent scalar-memory loads, and the plain body does all (1 + n) at once
+    __shared__ float s_exp[kExpTableSize];
+    for (int i = threadIdx.x; i < kExpTableSize; i += blockDim.x) s_exp[i] = c_exp_table[i];
+    __syncthreads();
+    // this wavefront's 128 draws in flight (two batches of 64, hot bit in bit 31), in LDS: the
+    // next pair's n draws go to lanes of `ids` with one ds_read, and no register holds the batches
+    // between refills (a wavefront's LDS accesses execute in order)
+    __shared__ uint32_t s_draws[4][128];
+    uint32_t *draws = s_draws[threadIdx.x >> 6];
+    // and its window of 128 walk positions (encoded rows, see chunk() below), for the same reason
+    __shared__ int s_walk[4][128];
+    int *wpos = s_walk[threadIdx.x >> 6];
 
     for (int64_t p = a.counter ? next_unit(a.counter, 0, 0, lane) : gw; p < a.P;
          p = next_unit(a.counter, p, nwaves, lane)) {
         const int32_t *__restrict__ walk = a.walks + p * (int64_t)a.L;
-        // ---- walk indices: positions [wbase, wbase + 128) in two VGPR chunks, slid forward.
-        // Each lane holds one position's row with its hot bit in bit 31 (gathered when the chunk
+        // ---- walk indices: positions [wbase, wbase + 128) in two chunks of 64, slid forward.
+        // Each entry holds one position's row with its hot bit in bit 31 (gathered when the chunk
         // is loaded, 64 positions ahead of use); -1 = None / past the end.
         auto chunk = [&](int q0) {
             const int q = q0 + lane;
@@ -861,18 +894,18 @@ __global__ void __launch_bounds__(256)
             return v;
         };
         int wbase = 0;
-        int c0 = chunk(0);
-        int c1 = chunk(64);
+        wpos[lane] = chunk(0);
+        wpos[64 + lane] = chunk(64);
+        __builtin_amdgcn_wave_barrier();
         auto raw_at = [&](int q) {  // encoded row of walk position q
             if (q >= path_len) return -1;
             while (q - wbase >= 128) {  // positions behind q - 2w are never asked for again
                 wbase += 64;
-                c0 = c1;
-                c1 = chunk(wbase + 64);
+                wpos[lane] = wpos[64 + lane];
+                wpos[64 + lane] = chunk(wbase + 64);
+                __builtin_amdgcn_wave_barrier();
             }
-            const int off = q - wbase;
-            return off < 64 ? __builtin_amdgcn_readlane(c0, off)
-                            : __builtin_amdgcn_readlane(c1, off - 64);
+            return uniform(wpos[q - wbase]);
         };
         // ---- pairs in the reference order (pyx:494-508): center i ascending, j ascending ----
         int it_i = 0, it_j = -1;
@@ -905,34 +938,35 @@ __global__ void __launch_bounds__(256)
         DrawPipe dp;
         dp.used = 0;
         dp.base0 = uniform64(a.seeds[p]);
-        dp.t0 = dp.t1 = 0;
         if (n > 0) {
-            dp.t0 = dp.gather_hot(dp.base0, lc, a);
+            draws[lane] = dp.gather_hot(dp.base0, lc, a);
             dp.base1 = advance64_uniform(dp.base0);
-            dp.t1 = dp.gather_hot(dp.base1, lc, a);
+            draws[64 + lane] = dp.gather_hot(dp.base1, lc, a);
+            __builtin_amdgcn_wave_barrier();
         }
-        auto take = [&](int k) -> uint32_t {
-            const int q = dp.used + k;
-            return q < 64 ? readlane_u32(dp.t0, q) : readlane_u32(dp.t1, q - 64);
-        };
         auto advance = [&]() {
             if (n == 0) return;
             dp.used += n;
             if (dp.used >= 64) {
                 dp.used -= 64;
-                dp.t0 = dp.t1;
+                draws[lane] = draws[64 + lane];
                 dp.base0 = dp.base1;
                 dp.base1 = advance64_uniform(dp.base1);
-                dp.t1 = dp.gather_hot(dp.base1, lc, a);
+                draws[64 + lane] = dp.gather_hot(dp.base1, lc, a);
+                __builtin_amdgcn_wave_barrier();
             }
         };
         // ---- the next pair: ids, hot bits, rows in flight ----
         int nci = -1, ncj = -1, npi = -1;
         bool nhi = false, nhj = false;
         int tn[MAXN + 1];
-        bool tnh[MAXN + 1];
         R in_n, pos_n, rn[MAXN + 1];
         int prev_i = -1;  // center of the pair just done
+        // The context-table rows of two consecutive pairs, one per lane, for the alias test: lanes
+        // [0, MAXN] hold the current pair's (ci, t[1..MAXN]), lanes [32, 32 + MAXN] the next
+        // pair's (nci, tn[1..MAXN]); draws carry their hot bit, a target past n is 0xFFFFFFFF.
+        static_assert(MAXN < 32, "the alias test keeps a pair's rows in half a wavefront");
+        uint32_t ids = 0xFFFFFFFFu;
         // rows of the pair next_pair() just produced.  Negative rows are read non-temporally:
         // random rows with little reuse, so the caches keep the packed negative table's words
         // and the hot bitmap instead (with the packed table: 105.7-106.0 vs 108.1 ms per C3
@@ -940,11 +974,13 @@ __global__ void __launch_bounds__(256)
         auto prefetch = [&](bool need_pos) {
             in_n.load(a.node + (int64_t)ncj * d, lane, d);
             if (need_pos) pos_n.load(a.ctx + (int64_t)nci * d, lane, d);
+            // lane 32 + k <- draw used + k - 1 (k <= n; used + n <= 127)
+            const bool drawn = lane > 32 && lane <= 32 + n;
+            const uint32_t nx = drawn ? draws[drawn ? dp.used + lane - 33 : 0] : 0xFFFFFFFFu;
+            ids = lane < 32 ? ids : lane == 32 ? (uint32_t)nci : nx;
 #pragma unroll
             for (int k = 1; k <= MAXN; ++k) {
-                const uint32_t raw = k <= n ? take(k - 1) : 0xFFFFFFFFu;
-                tn[k] = (int)(raw & ~kHotBit);
-                tnh[k] = (raw & kHotBit) != 0;
+                tn[k] = (int)(readlane_u32(ids, 32 + k) & ~kHotBit);
                 if (k > n) tn[k] = -1;
                 rn[k].load_nt(a.ctx + (int64_t)(valid_row(tn[k]) ? tn[k] : 0) * d, lane, d);
             }
@@ -961,41 +997,79 @@ __global__ void __launch_bounds__(256)
             const bool hot_ci = nhi, hot_cj = nhj;
             R in = in_n;
             int t[MAXN + 1];
-            bool th[MAXN + 1];
             R r[MAXN + 1];
 #pragma unroll
             for (int k = 1; k <= MAXN; ++k) {
                 t[k] = tn[k];
-                th[k] = tnh[k];
                 r[k] = rn[k];
             }
             const bool new_center = ic != prev_i;
             if (new_center || hot_ci) pos = pos_n;  // a hot positive is re-read for every pair
             if (new_center) pos_upd = false;
             prev_i = ic;
+            // the next pair's ids move to lanes [0, 32) (v_permlane32_swap: {lower, upper} halves
+            // broadcast); prefetch() then writes the pair after it into lanes [32, 32 + MAXN]
+            ids = (uint32_t)__builtin_amdgcn_permlane32_swap((int)ids, (int)ids, false, false)[1];
+            const uint32_t thm = (uint32_t)__ballot((ids & kHotBit) != 0);  // bit k: t[k] is hot
             // ---- put the pair after it in flight ----
             advance();
             have = next_pair(nci, ncj, npi, nhi, nhj);
             if (have) prefetch(npi != ic || nhi);
 
+            // ---- plain pair?  One test, as vector compares over `ids`: every draw of the pair
+            // is a row of the table (pyx:135's range), and no context-table row of this pair
+            // equals another row of it or a row of the next pair -- except the center, which the
+            // next pair usually shares (the carried positive; handled below for both paths).
+            // Then no target is skipped for its id, no negative repeats, and no prefetched copy
+            // needs a patch: the pair takes the straight-line body.  Node-table rows alias only
+            // as ncj == cj. ----
+            const uint32_t idv = ids & ~kHotBit;
+            uint64_t alias = __ballot(idv == (uint32_t)ci) & ~(1ull | (1ull << 32));
+#pragma unroll
+            for (int k = 1; k <= MAXN; ++k)  // t[k] == -1 past n: matches no lane of idv
+                alias |= __ballot(idv == (uint32_t)t[k]) & ~(1ull << k);
+            const uint64_t negs = (2ull << n) - 2ull;  // lanes 1..n
+            const bool plain = have && ncj != cj && alias == 0 &&
+                               (__ballot(idv < (uint32_t)a.V) & negs) == negs;
+
             // ---- the pair (pyx:128-149) ----
-            bool valid[MAXN + 1];
+            bool valid[MAXN + 1];  // general pairs only; a plain pair's n targets are all valid
 #pragma unroll
             for (int k = 1; k <= MAXN; ++k)
-                valid[k] = k <= n && t[k] != ci && valid_row(t[k]);  // pyx:135
+                valid[k] = !plain && k <= n && t[k] != ci && valid_row(t[k]);  // pyx:135
             float part[MAXN + 1];
             part[0] = lane_partial(in, pos);
 #pragma unroll
             for (int k = 1; k <= MAXN; ++k) part[k] = lane_partial(in, r[k]);
             wave_sum_n(part, n + 1);
+            // every lane holds every sum: keep target k's in lane k of one register
+            float fv = 0.0f;
+#pragma unroll
+            for (int k = 0; k <= MAXN; ++k) fv = lane == k ? part[k] : fv;
+            auto f_of = [&](int k) {
+                return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fv), k));
+            };
             R work;
 #pragma unroll
             for (int e = 0; e < VEC; ++e) work.v[e] = 0.0f;
+            // A plain pair's (1 + n) sigmoids at once: its dots are final (no target repeats), so
+            // skip test, bucket (the same f64 operations, pyx:141-143) and g (pyx:144) run across
+            // lanes, the table entry comes from LDS.  g_k replaces the dot in lane k and returns to
+            // a scalar by v_readlane; the targets to update are one bit mask.
+            uint64_t act = 0;
+            if (plain) {
+                const bool skip = fv <= -(float)kMaxExp || fv >= (float)kMaxExp;
+                int b = (int)(((double)fv + 6.0) * 83.0);
+                b = (uint32_t)b < (uint32_t)kExpTableSize ? b : 0;  // skipped lanes: any entry
+                act = __ballot(!skip) & ((2ull << n) - 1ull);  // targets 0..n
+                fv = (((lane == 0 ? 1.0f : 0.0f) - s_exp[b]) * a.lr) * a.alpha;  // now g_k
+            }
+            auto g_of = f_of;  // a plain pair's fv holds g_k
             float gpos = 0.0f;  // this pair's g of the positive (0 = skipped)
             {
-                float sig;
-                if (sigmoid_ref(uniformf(part[0]), &sig)) {
-                    const float g = ((1.0f - sig) * a.lr) * a.alpha;  // pyx:144
+                float sig = 0.0f;
+                if (plain ? (act & 1ull) != 0 : sigmoid_tab(s_exp, f_of(0), &sig)) {
+                    const float g = plain ? g_of(0) : ((1.0f - sig) * a.lr) * a.alpha;  // pyx:144
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) {
                         work.v[e] = __builtin_fmaf(g, pos.v[e], work.v[e]);  // pyx:146
@@ -1012,26 +1086,31 @@ __global__ void __launch_bounds__(256)
             for (int k = 1; k <= MAXN; ++k) {
                 upd[k] = false;
                 gk[k] = 0.0f;
-                if (!valid[k]) continue;
-                float f = part[k];
-                int prev = -1;  // latest earlier occurrence of the same negative row
+                float g;
+                if (plain) {
+                    if (!((act >> k) & 1ull)) continue;  // pyx:141-142, or k > n
+                    g = g_of(k);
+                } else {
+                    if (!valid[k]) continue;
+                    float f = f_of(k);
+                    int prev = -1;  // latest earlier occurrence of the same negative row
 #pragma unroll
-                for (int q = 1; q < k; ++q)
-                    if (valid[q] && t[q] == t[k]) prev = q;
-                if (prev >= 0) {
+                    for (int q = 1; q < k; ++q)
+                        if (valid[q] && t[q] == t[k]) prev = q;
+                    if (prev >= 0) {
 #pragma unroll
-                    for (int q = 1; q < k; ++q) {
-                        if (q == prev) {
-                            r[k] = r[q];
-                            f = upd[q] ? wave_sum(lane_partial(in, r[k])) : part[q];
+                        for (int q = 1; q < k; ++q) {
+                            if (q == prev) {
+                                r[k] = r[q];
+                                f = upd[q] ? uniformf(wave_sum(lane_partial(in, r[k]))) : f_of(q);
+                            }
                         }
+                        fv = lane == k ? f : fv;  // a later repeat may reuse this occurrence's dot
                     }
+                    float sig;
+                    if (!sigmoid_tab(s_exp, f, &sig)) continue;  // pyx:141-142
+                    g = ((0.0f - sig) * a.lr) * a.alpha;  // pyx:144, label 0
                 }
-                f = uniformf(f);
-                part[k] = f;
-                float sig;
-                if (!sigmoid_ref(f, &sig)) continue;  // pyx:141-142
-                const float g = ((0.0f - sig) * a.lr) * a.alpha;  // pyx:144, label 0
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) {
                     work.v[e] = __builtin_fmaf(g, r[k].v[e], work.v[e]);  // pyx:146
@@ -1056,12 +1135,12 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
             for (int k = 1; k <= MAXN; ++k) {
                 if (!upd[k]) continue;
-                if (th[k]) {
+                if ((thm >> k) & 1u) {
                     R dlt;  // this occurrence's change, g * in
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) dlt.v[e] = gk[k] * in.v[e];
                     dlt.atomic_add(a.ctx + (int64_t)t[k] * d, lane, d);
-                    if constexpr (VEC <= 2) {
+                    if (VEC <= 2 && !plain) {
 #pragma unroll
                         for (int q = 1; q <= MAXN; ++q)
                             if (tn[q] == t[k])
@@ -1073,14 +1152,14 @@ __global__ void __launch_bounds__(256)
                     }
                 } else {
                     r[k].store(a.ctx + (int64_t)t[k] * d, lane, d);
-                    if constexpr (VEC <= 2) {
+                    if (VEC <= 2 && !plain) {
 #pragma unroll
                         for (int q = 1; q <= MAXN; ++q)
                             if (tn[q] == t[k]) rn[q] = r[k];
                         if (have && nci == t[k] && (npi != ic || nhi)) pos_n = r[k];
                     }
                 }
-                if constexpr (VEC > 2) {
+                if (VEC > 2 && !plain) {
                     // wide rows: one patch for hot and cold copies, the row update's own fma
                     // (pyx:147) -- exact for a cold copy read after the previous store (it holds
                     // the row this pair updated), and without r[k] live past its store: 149
@@ -1107,19 +1186,21 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) pdl.v[e] = gpos * in.v[e];
                 pdl.atomic_add(a.ctx + (int64_t)ci * d, lane, d);
+                if (!plain)
 #pragma unroll
-                for (int q = 1; q <= MAXN; ++q)
-                    if (tn[q] == ci)
+                    for (int q = 1; q <= MAXN; ++q)
+                        if (tn[q] == ci)
 #pragma unroll
-                        for (int e = 0; e < VEC; ++e) rn[q].v[e] += pdl.v[e];
+                            for (int e = 0; e < VEC; ++e) rn[q].v[e] += pdl.v[e];
                 if (have && nci == ci)
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) pos_n.v[e] += pdl.v[e];
             } else if (!hot_ci && pos_upd && (!have || npi != ic)) {
                 pos.store(a.ctx + (int64_t)ci * d, lane, d);
+                if (!plain)
 #pragma unroll
-                for (int q = 1; q <= MAXN; ++q)
-                    if (tn[q] == ci) rn[q] = pos;
+                    for (int q = 1; q <= MAXN; ++q)
+                        if (tn[q] == ci) rn[q] = pos;
                 if (have && nci == ci) pos_n = pos;
             }
             // ---- the input row: in += work (pyx:149) ----
