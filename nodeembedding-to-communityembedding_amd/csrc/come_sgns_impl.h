@@ -218,6 +218,16 @@ __device__ inline void wave_sum_n(float (&part)[N], int count) {
 #undef COME_STAGE
 }
 
+// All N of `part[]`, with no branch per add: for a caller whose unused entries are initialised and
+// never read (the stream kernel: a lane past n holds a dot nobody looks at).
+template <int N>
+__device__ inline void wave_sum_all(float (&part)[N]) {
+#define COME_STAGE(S) \
+    _Pragma("unroll") for (int k = 0; k < N; ++k) part[k] = reduce_stage<S>(part[k]);
+    COME_STAGE(0) COME_STAGE(1) COME_STAGE(2) COME_STAGE(3) COME_STAGE(4) COME_STAGE(5)
+#undef COME_STAGE
+}
+
 // sigma lookup exactly as generated from pyx:141-143: skip if f <= -6 or f >= 6, else
 // EXP_TABLE[(int)(((double)f + 6.0) * 83.0)].  Returns false for a skipped target.
 __device__ inline bool sigmoid_ref(float f, float *sig) {
@@ -263,9 +273,12 @@ __device__ inline uint64_t draws_state_at_used(const DrawBatch &b, const LcgLane
     return lcg_next(uniform64(readlane_u64(s, 63)));
 }
 
-// Double-buffered draws: lanes of t0 hold draws base0 + lane, lanes of t1 the next 64.  The next
-// batch's table gather is issued as soon as the current one starts, so a pair never waits for
-// the table.  take(k) = target of draw `used + k` (used + k < 128).
+// Double-buffered draws: lanes of t0 hold draws base0 + lane, lanes of t1 the next 64.  The ring
+// kernel holds both batches in registers and issues the next batch's table gather as soon as the
+// current one starts, so its pairs never wait for the table; take(k) = target of draw `used + k`
+// (used + k < 128).  The stream kernel keeps the batches in LDS and uses gather_hot() alone: its
+// refill, every 64 draws, is synchronous -- the pair that triggers it waits for the gather's
+// dependent loads (LCG constants, table word, bitmap word) before the batch is written.
 struct DrawPipe {
     uint32_t t0, t1;
     uint64_t base0, base1;
@@ -821,12 +834,19 @@ __global__ void __launch_bounds__(128) k_sgns_o2_ring(O2Args a) {
 // 1% (the 1% bar of SURVEY.md §8c tier C).
 // Latency hiding as in the ring kernel, one pair ahead: the next pair's input row, its positive
 // (when the center changes or is hot), its negative rows and the hot bits of its rows are in
-// flight while the current pair computes; the next 64 table draws (with their hot bits) while the
-// current 64 are consumed.  A prefetched copy of a row the current pair then updates is patched:
-// a hot row's copy receives this wavefront's change additively (copy + delta: it keeps the other
-// wavefronts' atomics it was loaded with), a cold row's copy is replaced by the stored value (what
-// a read after the store returns; on walks that share no row the launch is bit-identical to the
-// sequential order, tests/test_gpu_stream.py).
+// flight while the current pair computes.  A prefetched copy of a row the current pair then
+// updates must not stay as it was read.  At d <= 128 the pair that updates such a row (a general
+// pair, below) waits for its write-backs and reads the next pair's rows again: a cold row's copy
+// then holds the stored value (on walks that share no row the launch is bit-identical to the
+// sequential order, tests/test_gpu_stream.py), a hot row's the memory after this wavefront's
+// atomic.  The one exception is a hot center's own change, added when the next pair of that
+// center takes the copy over (copy + delta: the copy keeps the other wavefronts' atomics it was
+// read with).  Wider rows patch the copies in registers.
+// The waits (d <= 128): vmcnt counts loads, stores and atomics in issue order, so a plain pair has
+// exactly one wait on it -- for the next pair's rows, placed before the pair's first store -- and
+// waits for no store or atomic; a general pair does, and so does the pair that refills the draws
+// or the walk positions (every 64 draws / positions).  profiles/r08_ab_straight_path.txt has the
+// loop's waits as compiled, before and after.
 // Two paths per pair.  On large tables nearly every pair is *plain*: its
 // context-table rows (center, n draws) are distinct rows of the table, none of them is a row of the
 // next pair (whose center may be the same), and the next pair has another input row.  One vector
@@ -838,10 +858,12 @@ __global__ void __launch_bounds__(128) k_sgns_o2_ring(O2Args a) {
 // What is wave-uniform per target lives in lanes, not in scalar registers: the dots / g_k (`fv`),
 // the rows and hot bits (`ids`); the draw batches and the walk's positions sit in LDS, read by
 // lane or by uniform address.
-// Wavefronts per SIMD the stream kernel is compiled for: the kernel is latency-bound (one pair of
-// loads in flight per wavefront), so at d <= 128, n <= 5 it is held to 64 VGPRs for 8 waves per
-// SIMD (a 32-byte spill): 108 vs 119 ms per C3 launch at the 7 waves 70 VGPRs would give
-// (profiles/r02_ab_stream_occupancy.txt).  Wider rows / more negatives keep their natural size:
+// Wavefronts per SIMD the stream kernel is compiled for: at d <= 128, n <= 5 it is held to 64
+// VGPRs for 8 waves per SIMD (a 20-byte spill, none of it inside the pair loop).  That was worth
+// 108 vs 119 ms per C3 launch against the 7 waves its natural 70 VGPRs give while every pair
+// waited for its stores (profiles/r02_ab_stream_occupancy.txt); with one wait per pair the two
+// are level, 724.7 vs 722.6 ms (profiles/r08_ab_straight_path.txt: 0.3%, less than three times
+// the spread, so the cap stays as it was).  Wider rows / more negatives keep their natural size:
 // C5's <4, true, 10> held to 4 waves per SIMD ran 3.57 vs 2.10 s per 1M-walk launch
 // (profiles/r05_ab_c5_waves.txt).
 template <int VEC, int MAXN>
@@ -863,8 +885,14 @@ __global__ void __launch_bounds__(256)
     const int w = a.window;  // <= 31 (launcher): lookups never fall behind the index window
     const int n = a.negative;
     const int path_len = a.L < kMaxSentenceLen ? a.L : kMaxSentenceLen;  // pyx:480
-    auto valid_row = [&](int r) { return r >= 0 && r < a.V; };
+    // V < 2^31 (launcher): one unsigned compare covers r >= 0 && r < V
+    const uint32_t Vu = (uint32_t)a.V;
+    auto valid_row = [&](int r) { return (uint32_t)r < Vu; };
+    // d <= 128: a general pair re-reads the next pair's rows after its write-backs instead of
+    // patching the prefetched registers (see the write-back below)
+    constexpr bool kReread = VEC <= 2;
     constexpr uint32_t kHotBit = 0x80000000u;
+    constexpr int kWaitVm0 = 0x0F70;  // s_waitcnt vmcnt(0), no other counter (gfx9 encoding)
     // the exp table in LDS, staged once per workgroup (4,000 bytes): a lookup is one ds_read
     // instead of two dependent scalar-memory loads, and the plain body does all (1 + n) at once
     __shared__ float s_exp[kExpTableSize];
@@ -959,8 +987,9 @@ __global__ void __launch_bounds__(256)
         // ---- the next pair: ids, hot bits, rows in flight ----
         int nci = -1, ncj = -1, npi = -1;
         bool nhi = false, nhj = false;
-        int tn[MAXN + 1];
         R in_n, pos_n, rn[MAXN + 1];
+        R padd;  // kReread: a hot center's change by this pair, owed to the next pair's copy
+        bool padd_on = false;
         int prev_i = -1;  // center of the pair just done
         // The context-table rows of two consecutive pairs, one per lane, for the alias test: lanes
         // [0, MAXN] hold the current pair's (ci, t[1..MAXN]), lanes [32, 32 + MAXN] the next
@@ -971,6 +1000,10 @@ __global__ void __launch_bounds__(256)
         // random rows with little reuse, so the caches keep the packed negative table's words
         // and the hot bitmap instead (with the packed table: 105.7-106.0 vs 108.1 ms per C3
         // launch; no gain with the plain table, profiles/r03_ab_nt_sites.txt)
+        // the next pair's k-th negative row, from lane 32 + k of `ids` (past n: no row)
+        auto next_target = [&](int k) {
+            return k <= n ? (int)(readlane_u32(ids, 32 + k) & ~kHotBit) : -1;
+        };
         auto prefetch = [&](bool need_pos) {
             in_n.load(a.node + (int64_t)ncj * d, lane, d);
             if (need_pos) pos_n.load(a.ctx + (int64_t)nci * d, lane, d);
@@ -980,13 +1013,24 @@ __global__ void __launch_bounds__(256)
             ids = lane < 32 ? ids : lane == 32 ? (uint32_t)nci : nx;
 #pragma unroll
             for (int k = 1; k <= MAXN; ++k) {
-                tn[k] = (int)(readlane_u32(ids, 32 + k) & ~kHotBit);
-                if (k > n) tn[k] = -1;
-                rn[k].load_nt(a.ctx + (int64_t)(valid_row(tn[k]) ? tn[k] : 0) * d, lane, d);
+                const int tk = next_target(k);
+                rn[k].load_nt(a.ctx + (int64_t)(valid_row(tk) ? tk : 0) * d, lane, d);
+            }
+        };
+        // The same rows again, past this CU's L1, once a general pair's write-backs are complete:
+        // every load then returns what its row holds after them.
+        auto reread = [&](bool need_pos) {
+            in_n.load_fresh(a.node + (int64_t)ncj * d, lane, d);
+            if (need_pos) pos_n.load_fresh(a.ctx + (int64_t)nci * d, lane, d);
+#pragma unroll
+            for (int k = 1; k <= MAXN; ++k) {
+                const int tk = next_target(k);
+                rn[k].load_fresh(a.ctx + (int64_t)(valid_row(tk) ? tk : 0) * d, lane, d);
             }
         };
         bool have = next_pair(nci, ncj, npi, nhi, nhj);
         if (have) prefetch(true);
+        if (kReread) __builtin_amdgcn_s_waitcnt(kWaitVm0);  // as after reread() below
         int nupd = 0;
         R pos;  // the current center's positive (carried across the center's pairs while cold)
         bool pos_upd = false;
@@ -1000,11 +1044,16 @@ __global__ void __launch_bounds__(256)
             R r[MAXN + 1];
 #pragma unroll
             for (int k = 1; k <= MAXN; ++k) {
-                t[k] = tn[k];
+                t[k] = next_target(k);
                 r[k] = rn[k];
             }
             const bool new_center = ic != prev_i;
-            if (new_center || hot_ci) pos = pos_n;  // a hot positive is re-read for every pair
+            if (new_center || hot_ci) {  // a hot positive is re-read for every pair
+                pos = pos_n;
+                if (kReread && padd_on)  // read before the last pair's atomic: copy + change
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) pos.v[e] += padd.v[e];
+            }
             if (new_center) pos_upd = false;
             prev_i = ic;
             // the next pair's ids move to lanes [0, 32) (v_permlane32_swap: {lower, upper} halves
@@ -1029,8 +1078,10 @@ __global__ void __launch_bounds__(256)
             for (int k = 1; k <= MAXN; ++k)  // t[k] == -1 past n: matches no lane of idv
                 alias |= __ballot(idv == (uint32_t)t[k]) & ~(1ull << k);
             const uint64_t negs = (2ull << n) - 2ull;  // lanes 1..n
+            // (kReread: nor is the next center, at another position, this center's row)
             const bool plain = have && ncj != cj && alias == 0 &&
-                               (__ballot(idv < (uint32_t)a.V) & negs) == negs;
+                               (__ballot(idv < Vu) & negs) == negs &&
+                               !(kReread && nci == ci && npi != ic);
 
             // ---- the pair (pyx:128-149) ----
             bool valid[MAXN + 1];  // general pairs only; a plain pair's n targets are all valid
@@ -1041,7 +1092,7 @@ __global__ void __launch_bounds__(256)
             part[0] = lane_partial(in, pos);
 #pragma unroll
             for (int k = 1; k <= MAXN; ++k) part[k] = lane_partial(in, r[k]);
-            wave_sum_n(part, n + 1);
+            wave_sum_all(part);  // past n: the dot of row 0, never read
             // every lane holds every sum: keep target k's in lane k of one register
             float fv = 0.0f;
 #pragma unroll
@@ -1120,18 +1171,27 @@ __global__ void __launch_bounds__(256)
                 gk[k] = g;
                 ++nupd;
             }
-            // ---- write-back: negatives (in order; a repeated row ends with its last version).
-            // Prefetched copies of the row (the next pair's targets, read before this store):
-            // hot -> + this occurrence's change (g * in; the memory-side atomics of other
-            // wavefronts that the copy was loaded with are kept); cold -> replaced by the stored
-            // value, exactly what a read after the store returns when no other wavefront wrote
-            // the row meanwhile (the cold case; a concurrent plain update in that window is lost,
-            // as in any plain read-modify-write of the reference's Hogwild) -- with walks that
-            // share no row the launch is then bit-identical to the sequential order.  Written as
-            // two branches: a select form of the same replacement let the compiler wait for the
-            // prefetched copies' loads (826 vs 803 ms per C3 launch; round 2's additive patch for
-            // every row 801 ms, not exact; re-reading the row after the store 803 ms;
-            // profiles/r04_ab_stream_patch.txt) ----
+            // ---- write-back: negatives (in order; a repeated row ends with its last version): a
+            // hot row receives this occurrence's change (g * in) as a float atomic at the memory
+            // side, a cold row is stored.  The next pair's rows were read before these writes.  A
+            // plain pair shares none of them.  After a general pair, d <= 128 (kReread): nothing
+            // is patched in registers -- the pair waits for its write-backs and reads the next
+            // pair's rows again (below), which returns the stored value of a cold row (with walks
+            // that share no row the launch stays bit-identical to the sequential order) and, for
+            // a hot row, the memory after this wavefront's atomic (the other wavefronts' included).
+            // Any assignment to the prefetched registers other than a load, even one skipped at
+            // run time, made the compiler copy them after every store and wait for the store
+            // (profiles/r08_ab_straight_path.txt).  Wide rows keep one patch for hot and cold
+            // copies, the row update's own fma (pyx:147) -- exact for a cold copy read after the
+            // previous store (it holds the row this pair updated), and without r[k] live past
+            // its store: 149 instead of 181 VGPRs at d = 256, n = 10 (3 waves per SIMD instead of
+            // 2: 2137 vs 2741 ms per C5 launch, profiles/r04_ab_stream_patch.txt) ----
+            // The pair's one wait for the next pair's rows stands here, before the first store:
+            // vmcnt counts loads, stores and atomics in issue order and how many targets a pair
+            // writes varies, so a wait placed after them (where the rows rotate next -> current)
+            // can only be vmcnt(0), a store round trip per pair.  Here the loads have had the
+            // whole pair to land, and the stores get the whole next pair.
+            if (kReread) __builtin_amdgcn_s_waitcnt(kWaitVm0);
 #pragma unroll
             for (int k = 1; k <= MAXN; ++k) {
                 if (!upd[k]) continue;
@@ -1140,35 +1200,13 @@ __global__ void __launch_bounds__(256)
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) dlt.v[e] = gk[k] * in.v[e];
                     dlt.atomic_add(a.ctx + (int64_t)t[k] * d, lane, d);
-                    if (VEC <= 2 && !plain) {
-#pragma unroll
-                        for (int q = 1; q <= MAXN; ++q)
-                            if (tn[q] == t[k])
-#pragma unroll
-                                for (int e = 0; e < VEC; ++e) rn[q].v[e] += dlt.v[e];
-                        if (have && nci == t[k] && (npi != ic || nhi))
-#pragma unroll
-                            for (int e = 0; e < VEC; ++e) pos_n.v[e] += dlt.v[e];
-                    }
                 } else {
                     r[k].store(a.ctx + (int64_t)t[k] * d, lane, d);
-                    if (VEC <= 2 && !plain) {
-#pragma unroll
-                        for (int q = 1; q <= MAXN; ++q)
-                            if (tn[q] == t[k]) rn[q] = r[k];
-                        if (have && nci == t[k] && (npi != ic || nhi)) pos_n = r[k];
-                    }
                 }
-                if (VEC > 2 && !plain) {
-                    // wide rows: one patch for hot and cold copies, the row update's own fma
-                    // (pyx:147) -- exact for a cold copy read after the previous store (it holds
-                    // the row this pair updated), and without r[k] live past its store: 149
-                    // instead of 181 VGPRs at d = 256, n = 10 (3 waves per SIMD instead of 2:
-                    // 2137 vs 2741 ms per C5 launch; at C3 the branch form above is 1.4% faster,
-                    // profiles/r04_ab_stream_patch.txt)
+                if (!kReread && !plain) {
 #pragma unroll
                     for (int q = 1; q <= MAXN; ++q)
-                        if (tn[q] == t[k])
+                        if (next_target(q) == t[k])
 #pragma unroll
                             for (int e = 0; e < VEC; ++e)
                                 rn[q].v[e] = __builtin_fmaf(gk[k], in.v[e], rn[q].v[e]);
@@ -1178,30 +1216,38 @@ __global__ void __launch_bounds__(256)
                             pos_n.v[e] = __builtin_fmaf(gk[k], in.v[e], pos_n.v[e]);
                 }
             }
-            // ---- the positive: hot -> this pair's change, g * in, now (memory side) and into the
-            // prefetched copies; cold -> stored once when the center ends, and its final value
-            // replaces prefetched copies (no other wavefront updates a cold row meanwhile)
+            // ---- the positive: hot -> this pair's change, g * in, now (memory side); the copy the
+            // next pair of this center has in flight predates it and receives it when that pair
+            // takes the copy over (padd).  Cold -> stored once when the center ends.
+            padd_on = false;
             if (hot_ci && gpos != 0.0f) {
                 R pdl;
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) pdl.v[e] = gpos * in.v[e];
                 pdl.atomic_add(a.ctx + (int64_t)ci * d, lane, d);
-                if (!plain)
+                if (kReread) {
+                    padd = pdl;
+                    padd_on = plain && nci == ci;
+                } else {
+                    if (!plain)
 #pragma unroll
-                    for (int q = 1; q <= MAXN; ++q)
-                        if (tn[q] == ci)
+                        for (int q = 1; q <= MAXN; ++q)
+                            if (next_target(q) == ci)
 #pragma unroll
-                            for (int e = 0; e < VEC; ++e) rn[q].v[e] += pdl.v[e];
-                if (have && nci == ci)
+                                for (int e = 0; e < VEC; ++e) rn[q].v[e] += pdl.v[e];
+                    if (have && nci == ci)
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) pos_n.v[e] += pdl.v[e];
+                        for (int e = 0; e < VEC; ++e) pos_n.v[e] += pdl.v[e];
+                }
             } else if (!hot_ci && pos_upd && (!have || npi != ic)) {
                 pos.store(a.ctx + (int64_t)ci * d, lane, d);
-                if (!plain)
+                if (!kReread) {
+                    if (!plain)
 #pragma unroll
-                    for (int q = 1; q <= MAXN; ++q)
-                        if (tn[q] == ci) rn[q] = pos;
-                if (have && nci == ci) pos_n = pos;
+                        for (int q = 1; q <= MAXN; ++q)
+                            if (next_target(q) == ci) rn[q] = pos;
+                    if (have && nci == ci) pos_n = pos;
+                }
             }
             // ---- the input row: in += work (pyx:149) ----
             if (hot_cj) {
@@ -1211,9 +1257,21 @@ __global__ void __launch_bounds__(256)
                 for (int e = 0; e < VEC; ++e) in.v[e] = in.v[e] + work.v[e];
                 in.store(a.node + (int64_t)cj * d, lane, d);
             }
-            if (have && ncj == cj)
+            if (kReread) {
+                if (!plain && have) {
+                    // every store and atomic of this pair acknowledged (vmcnt counts them with
+                    // the loads), then the next pair's rows again
+                    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+                    reread(npi != ic || nhi);
+                    // and landed: with a load pending on any way into the loop's header, the
+                    // compiler guards the header's uses with waits that also cover the stores
+                    // of a plain pair
+                    __builtin_amdgcn_s_waitcnt(kWaitVm0);
+                }
+            } else if (have && ncj == cj) {
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) in_n.v[e] += work.v[e];
+            }
         }
         if (a.upd_count && lane == 0 && nupd) atomicAdd(a.upd_count, (unsigned long long)nupd);
     }
