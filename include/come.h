@@ -469,7 +469,8 @@ int come_set_option(const char *name, int value);
  *           cached copy), while O1's run kernel (o1_chunk != 0) holds its input row -- hot or
  *           not -- over a run of consecutive edges sharing it and flushes the run's delta once
  *           (atomically when hot: other wavefronts' updates of the row during the run are kept,
- *           the run computes on its own copy).  The other rows are written back with plain
+ *           the run computes on its own copy; a hot row's delta also goes out before the second
+ *           update of a self-loop).  The other rows are written back with plain
  *           stores.  Ignored in COME_MODE_SEQUENTIAL.
  *           NULL: the library derives the bitmap from `table` on `stream` before EVERY launch
  *           (rows holding >= COME_DEFAULT_HOT_SHARE(_WIDE) of the table: a memset of V counters and a

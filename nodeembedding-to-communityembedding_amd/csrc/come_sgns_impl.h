@@ -1408,7 +1408,11 @@ __global__ void __launch_bounds__(256) k_sgns_o1(O1Args a) {
 // wavefront keeps node[u] in registers for the run of edges sharing u -- read once, updated by
 // every pair-1 of the run (pyx:444: input u) and read as pair 2's positive (pyx:447) -- and writes
 // it back once when u changes or the chunk ends: a float-atomic delta of the run's updates if u is
-// contended, else a plain store.  Any target row equal to the held u is taken from the registers.
+// contended, else a plain store.  A contended u's delta also goes out before the second update of
+// a self-loop (u, u), so that edge's two changes reach memory as two adds in order, exactly as
+// k_sgns_o1 sends them (tests/test_gpu_o1_hogwild.py: edges that share no row are bit-identical to
+// the sequential order under either kernel).  Any target row equal to the held u is taken from
+// the registers.
 // One wavefront in sequential mode: bit-identical to k_sgns_o1 (the held row is what memory holds).
 // Wavefronts per SIMD the run kernel is compiled for: latency-bound like the stream kernel (one
 // edge's rows in flight per wavefront), so at d <= 128, n <= 5 it is held to 64 VGPRs (a 12-byte
@@ -1541,10 +1545,14 @@ __global__ void __launch_bounds__(256)
                     for (int q = 0; q < VEC; ++q) work.v[q] = __builtin_fmaf(g, r2[k].v[q], work.v[q]);
                 }
                 if (v == u) {  // self-loop: pair 2 updates the held row itself
+                    // a contended row gets the self-loop's two changes as two atomics in order,
+                    // as k_sgns_o1 sends them (a run of one edge writes what that kernel writes):
+                    // the delta so far goes out now and pair 2's change starts the next one
+                    if (hot_cu) flush();
 #pragma unroll
                     for (int q = 0; q < VEC; ++q) {
                         hu.v[q] = hu.v[q] + work.v[q];
-                        du.v[q] = du.v[q] + work.v[q];
+                        du.v[q] = hot_cu ? work.v[q] : du.v[q] + work.v[q];
                     }
                 } else {
 #pragma unroll
