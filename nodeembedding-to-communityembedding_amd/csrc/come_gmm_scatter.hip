@@ -360,7 +360,8 @@ __global__ void __launch_bounds__((Cov16<D>::THREADS))
 // features x 16 samples, one ds_read_b128 per part) as the A operand of the tiles in row a and
 // the B operand of the tiles in column a: the 10 upper 32x32 tiles of a d = 128 component (3 at
 // d = 64) split 5 / 5 over two wavefronts.  sqrt(r) adds one rounding (1 ulp) to each weight
-// against the fp32 kernels' r d: tests hold the result to their tolerances and error level.
+// against the fp32 kernels' r d: tests hold the result to their tolerances and, at the chunk
+// lengths of 1M and 10M rows, to the error of a plain fp32 running sum.
 // Grid and output as k_gmm_cov16 (components per workgroup x row chunks, [chunk][K][d][d]).
 template <int D>
 struct CovBf3 {
@@ -441,6 +442,16 @@ __device__ __forceinline__ void covbf3_part(const CovArgs &a, const char *smb, i
     for (int n = 0; n < NT; ++n)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[n][e] = 0.0f;
+    // a2 b2 of the diagonal tiles, summed apart from acc.  It is 2^-18 of a1 b1 and a sum of
+    // squares on the diagonal of S_k: added to acc block by block it falls under half an ulp of
+    // S_ii after about a thousand rows of a chunk and vanishes from then on, in every chunk alike
+    // (S_ii 2.2e-6 low at 6 135 rows per chunk).  The other part products have zero mean there.
+    constexpr int NDG = 2;  // diagonal tiles per part
+    f32x16 accd[NDG];
+#pragma unroll
+    for (int n = 0; n < NDG; ++n)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) accd[n][e] = 0.0f;
     for (int j = 0; j < nb; ++j) {
         __syncthreads();  // barrier j: block j staged
         const char *im = smb + (j & 1) * C::BUF + tk * C::IMG;
@@ -458,7 +469,12 @@ __device__ __forceinline__ void covbf3_part(const CovArgs &a, const char *smb, i
             for (int n = 0; n < NT; ++n) {
                 const int ta = TT.ta[P][n], tb = TT.tb[P][n];
                 acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][2], F[tb][0], acc[n], 0, 0, 0);
-                acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], acc[n], 0, 0, 0);
+                if (ta == tb) {
+                    const int dg = TT.dslot(P, n);
+                    accd[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], accd[dg], 0, 0, 0);
+                } else {
+                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], acc[n], 0, 0, 0);
+                }
                 acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][2], acc[n], 0, 0, 0);
                 acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][0], acc[n], 0, 0, 0);
                 acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][1], acc[n], 0, 0, 0);
@@ -471,6 +487,7 @@ __device__ __forceinline__ void covbf3_part(const CovArgs &a, const char *smb, i
 #pragma unroll
     for (int n = 0; n < NT; ++n) {
         const int ta = TT.ta[P][n], tb = TT.tb[P][n];
+        if (ta == tb) acc[n] += accd[TT.dslot(P, n)];
         const int jj = 32 * tb + i;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -590,7 +607,9 @@ __global__ void __launch_bounds__(CovBf3<D>::THREADS) __attribute__((amdgpu_wave
 // 16-feature block transposed: lane i gets feature i of the 4 samples), so a staging lane's weight
 // is its own sample's (no broadcast) and its x is two 16-byte loads.  Diagonal tiles take their
 // cross terms a1 b2 + a2 b1 + a1 b3 + a3 b1 as U + U^T, U = a1 b2 + a1 b3: four MFMAs instead of six,
-// U^T added once at the end (3-5% faster than k_gmm_cov_bf3's six, whose bits it then leaves).
+// the transpose added once at the end (3-5% faster than k_gmm_cov_bf3's six, whose bits it then
+// leaves).  The second accumulator holds 2 U + a2 b2 and is halved at the end, which keeps a2 b2
+// out of the accumulator of a1 b1 (covbf3_part's accd).
 template <int D>
 struct CovFb3 {
     static_assert(D == 128, "k_gmm_cov_fb3 covers d = 128 (k_gmm_cov_bf3 takes d = 64)");
@@ -717,10 +736,17 @@ __device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, int nb,
         for (int n = 0; n < NT; ++n) {
             const int ta = TT.ta[P][n], tb = TT.tb[P][n];
             if (ta == tb) {
+                // accu = 2 U + a2 b2, halved with the transposition at the end: a2 b2 stays out
+                // of acc (covbf3_part's accd) at no register.  2 a1 is one exponent step up, one
+                // integer add per pair (a zero part becomes 2^-126, whose products vanish).
                 const int dg = TT.dslot(P, n);
-                accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][2], accu[dg], 0, 0, 0);
-                accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][1], accu[dg], 0, 0, 0);
-                acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], acc[n], 0, 0, 0);
+                const uint4 w = __builtin_bit_cast(uint4, F[ta][0]);
+                const bf16x8 a1x2 = __builtin_bit_cast(
+                    bf16x8, uint4{w.x + 0x00800080u, w.y + 0x00800080u, w.z + 0x00800080u,
+                                  w.w + 0x00800080u});
+                accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1x2, F[tb][2], accu[dg], 0, 0, 0);
+                accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1x2, F[tb][1], accu[dg], 0, 0, 0);
+                accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], accu[dg], 0, 0, 0);
                 acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][0], acc[n], 0, 0, 0);
                 continue;
             }
@@ -763,7 +789,7 @@ __device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, int nb,
             for (int r = 0; r < 16; ++r) u[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = accu[dg][r];
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                acc[n][r] += accu[dg][r] + u[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h];
+                acc[n][r] += 0.5f * (accu[dg][r] + u[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h]);
         }
     }
     float *out = a.out + (chunk * a.K + k0 + tk) * D * D;

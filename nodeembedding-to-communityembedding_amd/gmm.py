@@ -109,9 +109,12 @@ def scatter_chunks(V, K, d, cus):
     out, the partials <= 512 MB).  A ragged last round costs its whole length: at C4 (25 component
     pairs) 163 chunks = 7.96 rounds ran 7.44 ms, 168 (-> 169 used) = 8.25 rounds 7.75 ms
     (profiles/r05_ab_gmm_diag.txt).  Four rounds (81 chunks) ran 0.8% faster with the bf16-part
-    kernels but doubles each chunk's fp32 accumulation: their error against float64 then exceeds
-    1.5x the fp32 kernel's (test_c4_scatter_bf3_error_is_fp32_level; profiles/
-    r07_ab_scatter_fused.txt).  Other widths (the VALU kernel): ~8192 workgroups."""
+    kernels (profiles/r07_ab_scatter_fused.txt).  Other widths (the VALU kernel): ~8192
+    workgroups.  Each workgroup sums ceil(V / chunks) rows in fp32 -- 6 135 at V = 1M, K = 50,
+    d = 128, 61 350 at 10M -- and the chunks are then added in order; at those lengths every
+    kernel's error against float64 is held to 2x (RMS) / 3x (max) of a plain fp32 running sum of
+    the same rows in the same chunks (tests/test_gpu_scatter_accuracy.py, which takes its lengths
+    from this function)."""
     cap = max(1, min((128 << 20) // max(1, K * d * d), -(-V // 64)))
     if d not in (64, 128) or cus <= 0:
         return max(1, min(-(-8192 // K), cap))
