@@ -27,6 +27,12 @@
                   community_embeddings.community_loss end to end (factors derived, total read back).
                   Reference: the numpy / scipy formula (multivariate_normal.logpdf weighted by pi)
                   on a row subset, scaled to V.
+  --workload sgns_loss  the SGNS losses: on the C3 shape (1M nodes, d=128, negative=5, window=5,
+                  131,072 walks x 80, packed table) ms per come_sgns_o2_loss pass and per Hogwild
+                  come_sgns_o2 launch on the same walks in the same run, the loss timed again
+                  afterwards (same-run spread); then Node2Vec.loss native against torch on 1M
+                  edges of the graph taken in random order.  Roofline: (1 + n) rows per pair plus one centre row per centre against
+                  HBM (the naive (2 + n) rows per pair beside it).
 Each prints one JSON line.  CPU baselines on a bounded sample: O1 the builder's Hogwild C
 restatement of train_o1 (oracle/come_oracle_mt.c; reported beside it as the reference-equivalent
 rate, restatement / its calibrated speed-up over the reference's GIL-bound Node2Vec.train,
@@ -600,6 +606,106 @@ def community_loss_bench(args):
         "cpu_baseline": cpu}))
 
 
+def sgns_loss_bench(args):
+    import torch
+    import come_amd.training_sdg_inner as tsi
+    from come_amd.graph import chung_lu, random_walks
+    from come_amd.model import Model
+    from come_amd.node_embeddings import Node2Vec
+    dev = torch.device("cuda", 0)
+    n, d, w, L, B = args.negative, args.dim, 5, 80, 131072
+    g = chung_lu(args.nodes, 20.0, gamma=2.5, seed=1, device=dev)  # bench.py's C3 graph
+    V = g.V
+    B = min(B, V)
+    np.random.seed(1234)
+    m = Model(g.degree_by_id(), size=d, table_size=args.table_size, k=1, device=dev)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(100)
+    starts = torch.randperm(V, generator=gen, device=dev)[:B]
+    walks = random_walks(g, 0, L, seed=100, device=dev, starts=starts).contiguous()
+    gen.manual_seed(5678)
+    seeds = torch.randint(0, 2 ** 48, (B,), generator=gen, device=dev, dtype=torch.int64)
+    table = m.negative_table()
+    hot = m.hot_rows()
+    valid = walks >= 0
+    lengths = valid.sum(dim=1).long()
+    pairs = int(torch.where(lengths >= w + 1, 2 * w * lengths - w * (w + 1),
+                            lengths * (lengths - 1)).sum())
+    centres = int((valid & (lengths > 1)[:, None]).sum())
+    L_, ptr, stream = tsi._lib.lib(), tsi.ptr, tsi.stream_handle(dev)
+    tp, T, flag = tsi._table_args(table)
+    out = torch.zeros(2, dtype=torch.float64, device=dev)
+
+    def loss_pass():
+        tsi.check(L_.come_sgns_o2_loss(ptr(m.node_embedding), ptr(m.context_embedding), V, d,
+                                       ptr(walks), B, L, ptr(seeds), w, n, tp, T, flag, None,
+                                       ptr(out), ptr(out.view(torch.int64)[1:]), stream),
+                  "come_sgns_o2_loss")
+
+    def train_launch():
+        tsi.sgns_o2(m.node_embedding, m.context_embedding, walks, seeds, w, n, table, args.lr, 1.0,
+                    tsi.MODE_HOGWILD, hot=hot)
+    _, ks_l = timed(loss_pass, args.steps, args.warmup)
+    loss_before = float(out[0].item())
+    assert int(out.view(torch.int64)[1].item()) == pairs
+    _, ks_t = timed(train_launch, args.steps, args.warmup)
+    _, ks_l2 = timed(loss_pass, args.steps, args.warmup)  # again after training: same-run spread
+    loss_after = float(out[0].item())
+    tl, tt, tl2 = (float(np.mean(k)) for k in (ks_l, ks_t, ks_l2))
+    row = d * 4
+    model_bytes = ((1 + n) * pairs + centres) * row
+    naive_bytes = (2 + n) * pairs * row
+
+    # O1: Node2Vec.loss on 1M edges of the graph, native against the torch chain
+    E = min(1_000_000, g.num_edges)
+    edges = g.edge_ids()[np.random.RandomState(7).choice(g.num_edges, E, replace=False)]
+    n2v = Node2Vec()
+    rows = torch.from_numpy(n2v._edge_rows(m, edges)).to(dev)
+    r0, r1 = rows[:, 0].contiguous(), rows[:, 1].contiguous()
+    x = m.node_embedding
+
+    def o1_native():
+        return tsi.sgns_pairs_loss(x, x, r0, r1)[0]
+
+    def o1_torch():
+        rl = rows[(rows >= 0).all(dim=1)].long()
+        dots = (x[rl[:, 1]] * x[rl[:, 0]]).sum(dim=1).double()
+        return float(-torch.nn.functional.logsigmoid(dots).sum())
+    _, ks_n = timed(o1_native, args.steps, args.warmup)
+    _, ks_p = timed(o1_torch, args.steps, args.warmup)
+    _, ks_n2 = timed(o1_native, args.steps, args.warmup)
+    tn, tpt, tn2 = (float(np.mean(k)) for k in (ks_n, ks_p, ks_n2))
+    v_native, v_torch = n2v.loss(m, edges, backend='native'), n2v.loss(m, edges)
+    print(json.dumps({
+        "metric": "SGNS O2 loss, ms per pass, C3 shape (V=%d d=%d n=%d w=%d, %d walks x %d)"
+                  % (V, d, n, w, B, L),
+        "value": tl, "unit": "ms", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "higher_is_better": False, "dtype": "f32 dots, f64 softplus and sums",
+        "data": "synthetic (bench.py's C3 graph, walker seed 100)",
+        "config": {"workload": "come_sgns_o2_loss and the Hogwild come_sgns_o2 launch on the same "
+                               "%d walks, packed table; Node2Vec.loss on %d edges" % (B, E),
+                   "pairs": pairs, "centres": centres,
+                   "negative_table": "packed" if isinstance(table, tsi.PackedTable) else "uint32"},
+        "loss_ms": tl, "loss_ms_min": float(np.min(ks_l)), "loss_ms_second_timing": tl2,
+        "loss_ms_second_min": float(np.min(ks_l2)),
+        "train_ms": tt, "train_ms_min": float(np.min(ks_t)), "loss_over_train": tl / tt,
+        "second_loss_over_train": tl2 / tt,
+        "loss_total_before_training": loss_before, "loss_total_after_training": loss_after,
+        "roofline": {"bound": "hbm", "achieved": model_bytes / (tl / 1e3) / 1e9,
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": model_bytes / (tl / 1e3) / 1e9 / HBM_PEAK_GBS,
+                     "frac_second_timing": model_bytes / (tl2 / 1e3) / 1e9 / HBM_PEAK_GBS,
+                     "model": "(1 + n) rows per pair + one centre row per centre",
+                     "model_bytes": model_bytes, "naive_bytes": naive_bytes,
+                     "naive_frac": naive_bytes / (tl / 1e3) / 1e9 / HBM_PEAK_GBS,
+                     "avg_kernel_ms": tl},
+        "node2vec_loss": {"edges": E, "native_ms": tn, "native_ms_second_timing": tn2,
+                          "torch_ms": tpt, "native_over_torch": tn / tpt,
+                          "native_value": v_native, "torch_value": v_torch,
+                          "hbm_frac_native": 2.0 * E * row / (tn / 1e3) / 1e9 / HBM_PEAK_GBS},
+        "cpu_baseline": None}))
+
+
 def blas_threads():
     """Threads of the BLAS pool numpy / scipy / sklearn run on in this process (threadpoolctl),
     None if it cannot tell."""
@@ -613,7 +719,7 @@ def blas_threads():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["c2", "c4", "walks", "kmeans", "community_loss"], required=True)
+    ap.add_argument("--workload", choices=["c2", "c4", "walks", "kmeans", "community_loss", "sgns_loss"], required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dim", type=int, default=128)
@@ -643,7 +749,7 @@ def main():
             k, v = kv.split("=")
             _lib.set_option(k, int(v))
     {"c2": c2, "c4": c4, "walks": walks, "kmeans": kmeans_bench,
-     "community_loss": community_loss_bench}[args.workload](args)
+     "community_loss": community_loss_bench, "sgns_loss": sgns_loss_bench}[args.workload](args)
 
 
 if __name__ == "__main__":

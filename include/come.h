@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* ABI 5, additive: come_kmeans_pp_scratch, come_kmeans_pp_step, come_kmeans_pp_pick and
+/* ABI 5, additive: come_sgns_o2_loss, come_sgns_pairs_loss and their CPU twins (the SGNS
+ * objectives O2 / O1 evaluated natively; read-only on the tables).
+ * ABI 5, additive: come_kmeans_pp_scratch, come_kmeans_pp_step, come_kmeans_pp_pick and
  * come_kmeans_pp_sample (the greedy k-means++ seeding of come_amd.kmeans).
  * ABI 5, additive (the version is unchanged: nothing that existed moved): come_kmeans_scratch,
  * come_kmeans_lloyd, come_kmeans_assign and come_kmeans_update (k-means for the GMM init and
@@ -139,6 +141,50 @@ int come_pack_table(const uint32_t *table, uint64_t T, void *packed, int32_t *st
 int come_sgns_o1(float *node, int64_t V, int d, const int32_t *edges, int64_t E,
                  const uint64_t *seeds, int negative, const uint32_t *table, uint64_t T, float lr,
                  int mode, void *stream);
+
+/* ---- SGNS losses: the objective of a come_sgns_o2 batch, and of explicit pair lists ----
+ * For an input row a of table `inp`, a positive row b and negative rows t_1..t_n of table `out`:
+ *   pair(a; b; t) = softplus(-f(a, b)) + sum_k softplus(f(a, t_k)),   softplus(z) = log(1 + e^z)
+ * i.e. -log s(a.b) - sum_k log s(-a.t_k), the exact objective: neither the trainer's +-6 skip nor
+ * its 1000-entry sigmoid table.  f is the trainer's own fp32 dot (element e in lane e % 64, slot
+ * e / 64, an fmaf chain per lane in slot order, the lanes summed by the xor butterfly over offsets
+ * 1..32); softplus is evaluated in float64 on that fp32 value as max(z, 0) + log1p(exp(-|z|)).
+ * Summation order is part of the contract: a pair's terms are added in k order (k = 0 the
+ * positive) in float64, a walk's pairs in the trainer's pair order, and a total is the sum of the
+ * per-walk (per-pair) values in index order by a fixed tree (blocks of 4096 values: thread t of
+ * 256 adds values t, t + 256, ... then a halving tree; the block sums the same way).  No float or
+ * double atomics: every output is bit-identical from run to run, and the total does not depend on
+ * whether the per-walk / per-pair output is requested.  Both calls only read the tables, are
+ * asynchronous on `stream` and use library scratch that grows on demand (the first call at a
+ * larger P / M allocates: warm up before capturing a stream, as for come_sgns_o2_ex's bitmap).
+ * Tables, walks and row lists need only their natural 4-byte alignment.  P and M must be below
+ * 2^31 (COME_E_INVALID above; the CPU twins hold the same limit).
+ *
+ * come_sgns_o2_loss: the objective of exactly the batch come_sgns_o2 would train on with these
+ * walks and seeds.  Pairs as pyx:494-508 (centre i gives the positive row in ctx, every valid j of
+ * its window the input row in node, i outer, j inner; walk entries outside [0, V) are None); the
+ * `negative` draws of a pair are table[(next_random >> 16) % T] followed by the LCG step
+ * (pyx:133-134), next_random starting at seeds[p] and carried through the walk.  Every draw
+ * advances the LCG; a draw equal to the positive row (pyx:135) or outside [0, V) is skipped.
+ * flags: 0 or COME_TABLE_PACKED.  negative 0..20 (0: table may be NULL); any window >= 0;
+ * L <= 10000; 1 <= d <= 512.  walk_out: device float64 [P] or NULL; loss_out: one device double;
+ * pairs_out: one device int64 or NULL, = come_count_o2_pairs of the walks.  P = 0 is a no-op
+ * returning 0 that writes nothing; P > 0 without a pair writes 0.0 and 0.
+ *
+ * come_sgns_pairs_loss: explicit lists (held-out evaluation, O1): rows_in, rows_pos device int32
+ * [M], rows_neg device int32 [M x negative] row-major (NULL when negative = 0).  A pair whose
+ * input or positive row is outside [0, V) contributes 0 and is not counted; a negative outside
+ * [0, V) is skipped; a negative equal to the positive is used as given (the caller's list is the
+ * truth).  inp may equal out (O1).  pair_out: device float64 [M] or NULL; loss_out / pairs_out as
+ * above (pairs_out = the pairs counted).  M = 0 is a no-op returning 0. */
+int come_sgns_o2_loss(const float *node, const float *ctx, int64_t V, int d, const int32_t *walks,
+                      int64_t P, int L, const uint64_t *seeds, int window, int negative,
+                      const uint32_t *table, uint64_t T, int flags, double *walk_out,
+                      double *loss_out, int64_t *pairs_out, void *stream);
+int come_sgns_pairs_loss(const float *inp, const float *out, int64_t V, int d,
+                         const int32_t *rows_in, const int32_t *rows_pos, const int32_t *rows_neg,
+                         int64_t M, int negative, double *pair_out, double *loss_out,
+                         int64_t *pairs_out, void *stream);
 
 /* ---- Community gradient: replaces Community2Vec.train (community_embeddings.py:61-78) ----
  * x [V x d] updated in place, `iters` times:
@@ -515,7 +561,13 @@ int come_sgns_o1_ex(float *node, int64_t V, int d, const int32_t *edges, int64_t
  *  come_cpu_gmm_resp / _estep  community_embeddings.py:37 predict_proba; _estep adds lse_out.
  *  come_cpu_community_loss come_community_loss in float64 arithmetic (row_out [V] fp32 or NULL,
  *                          loss_out one host double); the total is summed per thread block of rows,
- *                          so it is reproducible for a given `threads`. */
+ *                          so it is reproducible for a given `threads`.
+ *  come_cpu_sgns_o2_loss / _pairs_loss  come_sgns_o2_loss / come_sgns_pairs_loss on host pointers
+ *                          (no flags: the uint32 table): the same dot, float64 softplus and
+ *                          summation order, so the per-walk / per-pair values differ from the
+ *                          GPU's by the two libms only and do not depend on `threads`; the total
+ *                          is summed per thread block of walks (pairs), so it is reproducible for
+ *                          a given `threads`.  pairs_out: one host int64 or NULL. */
 int come_cpu_sgns_o2(float *node, float *ctx, int64_t V, int d, const int32_t *walks, int64_t P,
                      int L, const uint64_t *seeds, int window, int negative, const uint32_t *table,
                      uint64_t T, float lr, float alpha, int mode, int threads, int64_t *pairs_out);
@@ -534,6 +586,14 @@ int come_cpu_gmm_estep(const float *x, int64_t V, int d, const float *prec_chol,
 int come_cpu_community_loss(const float *x, int64_t V, int d, const float *pi,
                             const float *prec_chol, const float *mu_prec, const float *log_norm,
                             int K, float *row_out, double *loss_out, int threads);
+int come_cpu_sgns_o2_loss(const float *node, const float *ctx, int64_t V, int d,
+                          const int32_t *walks, int64_t P, int L, const uint64_t *seeds,
+                          int window, int negative, const uint32_t *table, uint64_t T,
+                          double *walk_out, double *loss_out, int64_t *pairs_out, int threads);
+int come_cpu_sgns_pairs_loss(const float *inp, const float *out, int64_t V, int d,
+                             const int32_t *rows_in, const int32_t *rows_pos,
+                             const int32_t *rows_neg, int64_t M, int negative, double *pair_out,
+                             double *loss_out, int64_t *pairs_out, int threads);
 
 /* ---- Host helpers ---- */
 

@@ -34,7 +34,8 @@ SYMBOLS = ("come_abi_version", "come_last_error", "come_init", "come_exp_table",
            "come_source_sha256", "come_kmeans_scratch", "come_kmeans_lloyd",
            "come_kmeans_assign", "come_kmeans_update", "come_kmeans_pp_scratch",
            "come_kmeans_pp_step", "come_kmeans_pp_pick", "come_kmeans_pp_sample",
-           "come_community_loss", "come_cpu_community_loss")
+           "come_community_loss", "come_cpu_community_loss", "come_sgns_o2_loss",
+           "come_sgns_pairs_loss", "come_cpu_sgns_o2_loss", "come_cpu_sgns_pairs_loss")
 
 OPTION_FIELDS = ("o2_kernel", "o2_blocks_per_cu", "o2_waves_per_block",
                  "o2_static", "rows_per_wave", "o1_rows_per_wave",
@@ -136,6 +137,12 @@ def lib():
     L.come_cpu_gmm_resp.argtypes = [P, i64, i32, P, P, P, i32, P, i32]
     L.come_cpu_gmm_estep.argtypes = [P, i64, i32, P, P, P, i32, P, P, i32]
     L.come_cpu_community_loss.argtypes = [P, i64, i32, P, P, P, P, i32, P, P, i32]
+    L.come_sgns_o2_loss.argtypes = [P, P, i64, i32, P, i64, i32, P, i32, i32, P, u64, i32, P, P, P,
+                                    P]
+    L.come_sgns_pairs_loss.argtypes = [P, P, i64, i32, P, P, P, i64, i32, P, P, P, P]
+    L.come_cpu_sgns_o2_loss.argtypes = [P, P, i64, i32, P, i64, i32, P, i32, i32, P, u64, P, P, P,
+                                        i32]
+    L.come_cpu_sgns_pairs_loss.argtypes = [P, P, i64, i32, P, P, P, i64, i32, P, P, P, i32]
     cp = ctypes.c_char_p
     L.come_random_walks.argtypes = [P, P, i64, P, i64, i32, f32, u64, i64, P, P, P]
     L.come_walks_reference.argtypes = [P, P, i64, i32, P, P, i32, f64, P, i32, P]

@@ -100,6 +100,57 @@ class Context2Vec(object):
         ex.reset()
         return ex
 
+    def loss(self, model, paths, alpha=1.0, seeds=None, mean=False, return_pairs=False):
+        """alpha * O2 on ``paths``: the SGNS objective (training_sdg_inner.sgns_o2_loss -- exact
+        sigmoid, the trainer's pairs and negative draws, nothing written) of the batch ``train``
+        would see, so the full ComE objective can be followed during a run.  ``paths`` are mapped
+        as in ``train`` (walks_to_rows) and evaluated in ``batch_walks`` slices, totals and pair
+        counts added in float64 / int.  ``seeds``: every walk's initial next_random (uint64 [P]);
+        None takes them from a fixed private RandomState(0) stream in ``draw_seeds``' form -- never
+        from the global numpy RNG, which ``train`` draws from: a loss call does not shift a
+        training run.  ``mean=True`` divides by the pair count; ``return_pairs=True`` returns
+        ``(value, pair count)``.  Distributed: each rank evaluates its shard_walks shard, total
+        and pairs are all-reduced."""
+        import torch
+        rows = walks_to_rows(model, paths, max_len=tsi.MAX_SENTENCE_LEN)
+        P = rows.shape[0]
+        if seeds is None:
+            ab = np.random.RandomState(0).randint(0, 2 ** 24, size=2 * P).astype(np.uint64)
+            seeds = (ab[0::2] << np.uint64(24)) + ab[1::2]
+        elif not isinstance(seeds, torch.Tensor):
+            seeds = np.ascontiguousarray(seeds, np.uint64)
+        if seeds.shape != (P,):
+            raise ValueError("seeds must hold one value per walk (%d)" % P)
+        rank, world = self.world()
+        if world > 1:
+            from .distributed import shard_walks
+            rows, seeds = shard_walks(rows, seeds, rank, world)
+        dev = model.node_embedding.device
+        table = model.negative_table() if self.negative > 0 else None
+        total, pairs = 0.0, 0
+        for b in range(0, rows.shape[0], self.batch_walks):
+            w = rows[b:b + self.batch_walks]
+            w = w.contiguous() if isinstance(w, torch.Tensor) else \
+                torch.from_numpy(np.ascontiguousarray(w, np.int32)).to(dev)
+            sd = seeds[b:b + self.batch_walks]
+            sd = sd.contiguous() if isinstance(sd, torch.Tensor) else \
+                torch.from_numpy(np.ascontiguousarray(sd, np.uint64).view(np.int64)).to(dev)
+            t, p = tsi.sgns_o2_loss(model.node_embedding, model.context_embedding, w, sd,
+                                    self.window_size, self.negative, table)
+            total += t
+            pairs += p
+        if world > 1:
+            from .distributed import all_reduce_sum
+            tt = torch.tensor([total], dtype=torch.float64, device=dev)
+            pp = torch.tensor([pairs], dtype=torch.int64, device=dev)
+            all_reduce_sum([tt], self.group)
+            all_reduce_sum([pp], self.group)
+            total, pairs = float(tt[0]), int(pp[0])
+        value = alpha * total
+        if mean:
+            value = value / pairs if pairs else 0.0
+        return (value, pairs) if return_pairs else value
+
     def train(self, model, paths, total_nodes, alpha=1.0, node_count=0, chunksize=150):
         """Train the context embedding on ``paths`` (iterable of node-id walks, a [P, L] id
         array, or a CUDA id tensor [P, L] with -1 after each walk's end -- converted and trained

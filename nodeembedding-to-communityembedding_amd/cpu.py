@@ -8,6 +8,8 @@ to them.
     community_grad(x, pi, mu, inv_cov, beta, lr, iters, threads)    (community_embeddings.py:61-78)
     gmm_estep(x, prec_chol, mu_prec, log_norm, threads) -> (resp, lse)  (predict_proba, :37)
     community_loss(x, pi, prec_chol, mu_prec, log_norm, threads) -> total   (what :40-59 means)
+    sgns_o2_loss(node, ctx, walks, seeds, window, negative, table) -> (total, pairs[, per walk])
+    sgns_pairs_loss(inp, out, rows_in, rows_pos, rows_neg)         -> (total, counted[, per pair])
 
 Tables are updated in place (float32, C-contiguous, as the reference's numpy arrays).  ``mode``:
 MODE_HOGWILD = ``threads`` workers taking jobs of 150 walks / edges with lock-free updates, as the
@@ -132,3 +134,55 @@ def community_loss(x, pi, prec_chol, mu_prec, log_norm, return_rows=False, threa
                                              ctypes.byref(total), _threads(threads)),
           "come_cpu_community_loss")
     return (total.value, rows) if return_rows else total.value
+
+
+def sgns_o2_loss(node, ctx, walks, seeds, window, negative, table, return_walks=False,
+                 threads=None):
+    """come_cpu_sgns_o2_loss: the SGNS objective of the batch ``sgns_o2`` would train on with these
+    walk rows [P, L] int32 and seeds (uint64 [P]) -- the trainer's pairs, LCG negatives and fp32
+    dot, a float64 softplus, nothing written.  ``table``: uint32 [T] (None with negative = 0).
+    Returns ``(total, pairs)``, or ``(total, pairs, per_walk float64 [P])`` with
+    ``return_walks``; per_walk does not depend on ``threads``."""
+    _arr(node, np.float32, "node")
+    _arr(ctx, np.float32, "ctx")
+    _arr(walks, np.int32, "walks")
+    _arr(seeds, np.uint64, "seeds")
+    if table is not None:
+        _arr(table, np.uint32, "table")
+    assert node.shape == ctx.shape and walks.ndim == 2 and seeds.shape == (walks.shape[0],)
+    P = walks.shape[0]
+    per_walk = np.zeros(P, np.float64) if return_walks else None
+    total, pairs = ctypes.c_double(0.0), ctypes.c_int64(0)
+    check(_lib.lib().come_cpu_sgns_o2_loss(
+        ptr(node), ptr(ctx), node.shape[0], node.shape[1], ptr(walks), P, walks.shape[1],
+        ptr(seeds), int(window), int(negative), None if table is None else ptr(table),
+        0 if table is None else len(table), ptr(per_walk) if return_walks else None,
+        ctypes.byref(total), ctypes.byref(pairs), _threads(threads)), "come_cpu_sgns_o2_loss")
+    return (total.value, pairs.value, per_walk) if return_walks else (total.value, pairs.value)
+
+
+def sgns_pairs_loss(inp, out, rows_in, rows_pos, rows_neg=None, return_pairs=False, threads=None):
+    """come_cpu_sgns_pairs_loss: the SGNS objective of explicit lists -- input rows ``rows_in`` [M]
+    of ``inp``, positive rows ``rows_pos`` [M] and negative rows ``rows_neg`` [M, n] (or None) of
+    ``out``, int32.  Returns ``(total, counted)``, or ``(total, counted, per_pair float64 [M])``
+    with ``return_pairs``."""
+    _arr(inp, np.float32, "inp")
+    _arr(out, np.float32, "out")
+    _arr(rows_in, np.int32, "rows_in")
+    _arr(rows_pos, np.int32, "rows_pos")
+    M = rows_in.shape[0]
+    n = 0
+    if rows_neg is not None:
+        _arr(rows_neg, np.int32, "rows_neg")
+        assert rows_neg.ndim == 2 and rows_neg.shape[0] == M
+        n = rows_neg.shape[1]
+    assert inp.shape == out.shape and rows_in.ndim == 1 and rows_pos.shape == (M,)
+    per_pair = np.zeros(M, np.float64) if return_pairs else None
+    total, counted = ctypes.c_double(0.0), ctypes.c_int64(0)
+    check(_lib.lib().come_cpu_sgns_pairs_loss(
+        ptr(inp), ptr(out), inp.shape[0], inp.shape[1], ptr(rows_in), ptr(rows_pos),
+        ptr(rows_neg) if n else None, M, n, ptr(per_pair) if return_pairs else None,
+        ctypes.byref(total), ctypes.byref(counted), _threads(threads)),
+          "come_cpu_sgns_pairs_loss")
+    return (total.value, counted.value, per_pair) if return_pairs else (total.value,
+                                                                         counted.value)

@@ -20,6 +20,10 @@
 //                            E-step's per-row log-sum-exp, rows split over the threads.
 //   come_cpu_community_loss  the community objective (what community_embeddings.py:40-59 means),
 //                            float64 arithmetic, one partial sum per thread's block of rows.
+//   come_cpu_sgns_o2_loss / _pairs_loss  the SGNS objectives as come_sgns_o2_loss /
+//                            come_sgns_pairs_loss define them: the trainer's fp32 WAVE64 dot, a
+//                            float64 softplus on it, terms added in k order, pairs in the
+//                            trainer's order; one partial sum per thread's block of walks (pairs).
 // Each compute body is built twice, for AVX2+FMA and for the baseline ISA (explicit fmaf either
 // way, -ffp-contract=off: identical results), and the first call picks one from the CPU.
 #include <stdint.h>
@@ -391,6 +395,129 @@ int check_sgns(int64_t V, int d, int negative, const uint32_t *table, uint64_t T
     return check_threads(threads);
 }
 
+// ---- the SGNS objectives as losses (come_sgns_loss.hip's arithmetic and summation order) ----
+struct SgnsLoss {
+    const float *in_tab, *out_tab;
+    int64_t V;
+    int d, negative, window, L;
+    const int32_t *walks;      // O2: [P x L]
+    const uint64_t *seeds;     // O2: [P]
+    const uint32_t *table;     // O2
+    uint64_t T;
+    const int32_t *rows_in, *rows_pos, *rows_neg;  // explicit pairs
+    double *unit_out;          // per walk / per pair, or null
+};
+
+HOT double softplus64(double z) { return std::fmax(z, 0.0) + std::log1p(std::exp(-std::fabs(z))); }
+
+// softplus(-f(in, pos)) + sum_k softplus(f(in, t_k)) added in k order from the positive; a target
+// equal to `skip` or outside [0, V) adds nothing.
+template <bool Simd>
+HOT double pair_loss(const SgnsLoss &a, int64_t ri, int64_t rp, const uint32_t *target, int64_t skip) {
+    const float *in = a.in_tab + ri * a.d;
+    auto dot = [&](const float *o) {
+        if constexpr (Simd) return (a.d & 63) == 0 ? dot_wave64_avx2(in, o, a.d) : dot_wave64(in, o, a.d);
+        else return dot_wave64(in, o, a.d);
+    };
+    double s = 0.0;
+    s += softplus64(-(double)dot(a.out_tab + rp * a.d));
+    for (int k = 0; k < a.negative; ++k) {
+        const int64_t t = (int64_t)target[k];
+        if (t == skip || t >= a.V) continue;
+        s += softplus64((double)dot(a.out_tab + t * a.d));
+    }
+    return s;
+}
+
+// train_o2's enumeration and draws on walk p (walk_o2 above), nothing written: the walk's value.
+template <bool Simd>
+HOT double walk_loss(const SgnsLoss &a, int64_t p, int64_t *pairs) {
+    const int32_t *idx = a.walks + p * (int64_t)a.L;
+    const int n = a.L < kMaxSentenceLen ? a.L : kMaxSentenceLen;
+    auto ok = [&](int j) { return idx[j] >= 0 && (int64_t)idx[j] < a.V; };
+    uint64_t nr = a.seeds[p];
+    uint32_t target[kMaxNegative];
+    double total = 0.0;
+    for (int i = 0; i < n; ++i) {
+        if (!ok(i)) continue;
+        const int j0 = i - a.window < 0 ? 0 : i - a.window;
+        const int j1 = (int64_t)i + a.window + 1 > n ? n : i + a.window + 1;
+        for (int j = j0; j < j1; ++j) {
+            if (j == i || !ok(j)) continue;
+            for (int k = 0; k < a.negative; ++k) {
+                target[k] = a.table[(nr >> 16) % a.T];
+                nr = (nr * kLcgMul + kLcgAdd) & kLcgMask;  // pyx:134: every draw advances
+            }
+            total += pair_loss<Simd>(a, idx[j], idx[i], target, idx[i]);
+            ++*pairs;
+        }
+    }
+    return total;
+}
+
+// units lo .. hi - 1 (walks, or explicit pairs when a.walks is null), added in index order
+template <bool Simd>
+HOT double loss_units(const SgnsLoss &a, int64_t lo, int64_t hi, int64_t *pairs) {
+    double total = 0.0;
+    for (int64_t u = lo; u < hi; ++u) {
+        double v = 0.0;
+        if (a.walks || a.seeds) {
+            v = walk_loss<Simd>(a, u, pairs);
+        } else {
+            const int64_t ri = a.rows_in[u], rp = a.rows_pos[u];
+            if (ri >= 0 && ri < a.V && rp >= 0 && rp < a.V) {
+                v = pair_loss<Simd>(a, ri, rp, reinterpret_cast<const uint32_t *>(a.rows_neg) +
+                                                   u * (int64_t)a.negative, -1);
+                ++*pairs;
+            }
+        }
+        if (a.unit_out) a.unit_out[u] = v;
+        total += v;
+    }
+    return total;
+}
+COME_FMA_CLONE double loss_units_fma(const SgnsLoss &a, int64_t lo, int64_t hi, int64_t *pairs) {
+    return loss_units<true>(a, lo, hi, pairs);
+}
+double loss_units_base(const SgnsLoss &a, int64_t lo, int64_t hi, int64_t *pairs) {
+    return loss_units<false>(a, lo, hi, pairs);
+}
+
+// one partial per block of units (parallel_rows' split), added in block order
+void loss_drive(const SgnsLoss &a, int64_t units, int threads, double *loss_out,
+                int64_t *pairs_out) {
+    auto fn = have_fma() ? loss_units_fma : loss_units_base;
+    const int64_t per = threads <= 1 || units < 64 ? units : (units + threads - 1) / threads;
+    const size_t blocks = (size_t)((units + per - 1) / per);
+    std::vector<double> part(blocks, 0.0);
+    std::vector<int64_t> cnt(blocks, 0);
+    parallel_rows(units, threads, [&](int64_t lo, int64_t hi) {
+        part[lo / per] = fn(a, lo, hi, &cnt[lo / per]);
+    });
+    double total = 0.0;
+    int64_t pairs = 0;
+    for (size_t b = 0; b < blocks; ++b) {
+        total += part[b];
+        pairs += cnt[b];
+    }
+    *loss_out = total;
+    if (pairs_out) *pairs_out = pairs;
+}
+
+// come_sgns_o2_loss's messages (the GPU entry validates the same way)
+int check_loss_tables(const char *who, int64_t V, int d, int negative) {
+    if (V <= 0) return set_error(COME_E_INVALID, "%s: V must be > 0 (got %lld)", who, (long long)V);
+    if (V > INT32_MAX)
+        return set_error(COME_E_INVALID, "%s: V must fit int32 row indices (got %lld)", who,
+                         (long long)V);
+    if (d < 1 || d > kMaxDim)
+        return set_error(COME_E_INVALID, "%s: d must be in [1, %d] (got %d)", who, kMaxDim, d);
+    if (negative < 0 || negative > kMaxNegative)
+        return set_error(COME_E_INVALID, "%s: negative must be in [0, %d] (got %d)", who,
+                         kMaxNegative, negative);
+    return COME_OK;
+}
+
 }  // namespace
 
 extern "C" int come_cpu_sgns_o2(float *node, float *ctx, int64_t V, int d, const int32_t *walks,
@@ -486,4 +613,53 @@ extern "C" int come_cpu_gmm_resp(const float *x, int64_t V, int d, const float *
                                  float *resp_out, int threads) {
     return come_cpu_gmm_estep(x, V, d, prec_chol, mu_prec, log_norm, K, resp_out, nullptr,
                               threads);
+}
+
+extern "C" int come_cpu_sgns_o2_loss(const float *node, const float *ctx, int64_t V, int d,
+                                     const int32_t *walks, int64_t P, int L,
+                                     const uint64_t *seeds, int window, int negative,
+                                     const uint32_t *table, uint64_t T, double *walk_out,
+                                     double *loss_out, int64_t *pairs_out, int threads) {
+    int rc = check_loss_tables("cpu_sgns_o2_loss", V, d, negative);
+    if (rc) return rc;
+    if (negative > 0 && (!table || T == 0))
+        return set_error(COME_E_INVALID,
+                         "cpu_sgns_o2_loss: negative sampling needs a non-empty table");
+    if (P < 0 || L < 0 || window < 0)
+        return set_error(COME_E_INVALID, "cpu_sgns_o2_loss: P, L and window must be >= 0");
+    if (L > kMaxSentenceLen)
+        return set_error(COME_E_INVALID, "cpu_sgns_o2_loss: L must be <= %d (got %d)",
+                         kMaxSentenceLen, L);
+    if (P > INT32_MAX) return set_error(COME_E_INVALID, "cpu_sgns_o2_loss: P too large");
+    rc = check_threads(threads);
+    if (rc) return rc;
+    if (P == 0) return COME_OK;
+    if (!node || !ctx || (!walks && L > 0) || !seeds || !loss_out)
+        return set_error(COME_E_INVALID,
+                         "cpu_sgns_o2_loss: null node/ctx/walks/seeds/loss_out pointer");
+    const SgnsLoss a{node,  ctx, V,       d,       negative, window,  L,       walks,
+                     seeds, table, T, nullptr, nullptr,  nullptr, walk_out};
+    loss_drive(a, P, threads, loss_out, pairs_out);
+    return COME_OK;
+}
+
+extern "C" int come_cpu_sgns_pairs_loss(const float *inp, const float *out, int64_t V, int d,
+                                        const int32_t *rows_in, const int32_t *rows_pos,
+                                        const int32_t *rows_neg, int64_t M, int negative,
+                                        double *pair_out, double *loss_out, int64_t *pairs_out,
+                                        int threads) {
+    int rc = check_loss_tables("cpu_sgns_pairs_loss", V, d, negative);
+    if (rc) return rc;
+    if (M < 0) return set_error(COME_E_INVALID, "cpu_sgns_pairs_loss: M must be >= 0");
+    if (M > INT32_MAX) return set_error(COME_E_INVALID, "cpu_sgns_pairs_loss: M too large");
+    rc = check_threads(threads);
+    if (rc) return rc;
+    if (M == 0) return COME_OK;
+    if (!inp || !out || !rows_in || !rows_pos || (!rows_neg && negative > 0) || !loss_out)
+        return set_error(COME_E_INVALID, "cpu_sgns_pairs_loss: null inp/out/rows_in/rows_pos/"
+                                         "rows_neg/loss_out pointer");
+    const SgnsLoss a{inp,     out,     V, d,       negative, 0,        0,       nullptr,
+                     nullptr, nullptr, 0, rows_in, rows_pos, rows_neg, pair_out};
+    loss_drive(a, M, threads, loss_out, pairs_out);
+    return COME_OK;
 }

@@ -6,7 +6,8 @@ edge draws its own next_random from the global numpy RNG in edge order (pyx:427)
 trains the pairs (edge[0] -> edge[1]) then (edge[1] -> edge[0]) on node_embedding only
 (pyx:444-448).  One launch per pass over the edges (passes stay ordered), one wavefront per edge
 (Hogwild across edges) or, with ``deterministic=True``, one wavefront in edge order (== the
-reference with workers=1).  ``loss`` reproduces :26-31 (-sum log sigma(u.v) over the edges).
+reference with workers=1).  ``loss`` reproduces :26-31 (-sum log sigma(u.v) over the edges;
+``backend='native'`` evaluates it in one kernel launch).
 
 Multi-GPU (``distributed=True``): every rank is handed the same edge list, draws
 every edge's seed per pass (the global numpy RNG advances as in one process), trains its
@@ -98,8 +99,18 @@ class Node2Vec(object):
         rows[bad] = -1
         return rows.astype(np.int32)
 
-    def loss(self, model, edges):
+    def loss(self, model, edges, backend='torch'):
+        """-sum log sigma(x_v . x_u) over the valid edges (:26-31).  backend 'torch' (default): a
+        gather-multiply-sum chain with two [E x d] temporaries; 'native': one
+        training_sdg_inner.sgns_pairs_loss launch (no negatives, no temporaries; the trainer's
+        fp32 dot order, float64 softplus)."""
         import torch
+        if backend == 'native':
+            rows = torch.from_numpy(self._edge_rows(model, edges)).to(model.node_embedding.device)
+            x = model.node_embedding
+            return tsi.sgns_pairs_loss(x, x, rows[:, 0].contiguous(), rows[:, 1].contiguous())[0]
+        if backend != 'torch':
+            raise ValueError("backend must be 'torch' or 'native'")
         rows = torch.from_numpy(self._edge_rows(model, edges)).to(model.node_embedding.device)
         rows = rows[(rows >= 0).all(dim=1)].long()
         x = model.node_embedding

@@ -238,6 +238,79 @@ def sgns_o1(node, edges, seeds, negative, table, lr, mode=MODE_HOGWILD, opts=Non
     check(rc, "come_sgns_o1")
 
 
+def sgns_o2_loss(node, ctx, walks, seeds, window, negative, table, return_walks=False):
+    """The SGNS objective of exactly the batch ``sgns_o2`` would train on with these ``walks`` [P, L]
+    and ``seeds`` [P] (come_sgns_o2_loss: same pairs, same LCG negatives, the trainer's fp32 dot,
+    float64 softplus, nothing written to the tables).  Arguments as ``sgns_o2``; ``table`` may be
+    a PackedTable (with negative = 0 it may be None).  Returns ``(total, pairs)`` as a Python float
+    and int, or ``(total, pairs, per_walk)`` with a CUDA float64 tensor [P] when
+    ``return_walks``."""
+    import torch
+    _require_cuda(node, "node", torch.float32)
+    _require_cuda(ctx, "ctx", torch.float32)
+    _require_cuda(walks, "walks", torch.int32)
+    _require_cuda(seeds, "seeds", torch.int64)
+    tp, T, flag = (None, 0, 0) if table is None else _table_args(table)
+    if node.shape != ctx.shape or node.dim() != 2:
+        raise ValueError("node and ctx must both be [V, d]")
+    if walks.dim() != 2 or seeds.shape != (walks.shape[0],):
+        raise ValueError("walks must be [P, L] and seeds [P]")
+    if walks.shape[1] > MAX_SENTENCE_LEN:  # as sgns_o2 (pyx:480)
+        walks = walks[:, :MAX_SENTENCE_LEN].contiguous()
+    V, d = node.shape
+    P = walks.shape[0]
+    per_walk = torch.zeros(P, dtype=torch.float64, device=node.device) if return_walks else None
+    if P:
+        out = torch.zeros(2, dtype=torch.float64, device=node.device)  # the total, then the count
+        rc = _lib.lib().come_sgns_o2_loss(
+            ptr(node), ptr(ctx), V, d, ptr(walks), P, walks.shape[1], ptr(seeds), int(window),
+            int(negative), tp, T, flag, ptr(per_walk) if return_walks else None, ptr(out),
+            ptr(out.view(torch.int64)[1:]), stream_handle(node.device))
+        check(rc, "come_sgns_o2_loss")
+        total, pairs = float(out[0].item()), int(out.view(torch.int64)[1].item())
+    else:
+        total, pairs = 0.0, 0
+    return (total, pairs, per_walk) if return_walks else (total, pairs)
+
+
+def sgns_pairs_loss(inp, out, rows_in, rows_pos, rows_neg=None, return_pairs=False):
+    """The SGNS objective of explicit pair lists (come_sgns_pairs_loss): input rows ``rows_in`` [M]
+    of ``inp``, positive rows ``rows_pos`` [M] and negative rows ``rows_neg`` [M, n] (or None: no
+    negatives) of ``out`` -- CUDA int32.  A pair with an input or positive row outside [0, V) is
+    not counted, a negative outside it is skipped, a negative equal to the positive is used as
+    given.  ``inp`` may be ``out`` (O1).  Returns ``(total, counted)``, or ``(total, counted,
+    per_pair)`` with a CUDA float64 tensor [M] when ``return_pairs``."""
+    import torch
+    _require_cuda(inp, "inp", torch.float32)
+    _require_cuda(out, "out", torch.float32)
+    _require_cuda(rows_in, "rows_in", torch.int32)
+    _require_cuda(rows_pos, "rows_pos", torch.int32)
+    if inp.shape != out.shape or inp.dim() != 2:
+        raise ValueError("inp and out must both be [V, d]")
+    M = rows_in.shape[0]
+    if rows_in.dim() != 1 or rows_pos.shape != (M,):
+        raise ValueError("rows_in and rows_pos must both be [M]")
+    n = 0
+    if rows_neg is not None:
+        _require_cuda(rows_neg, "rows_neg", torch.int32)
+        if rows_neg.dim() != 2 or rows_neg.shape[0] != M:
+            raise ValueError("rows_neg must be [M, n]")
+        n = rows_neg.shape[1]
+    V, d = inp.shape
+    per_pair = torch.zeros(M, dtype=torch.float64, device=inp.device) if return_pairs else None
+    if M:
+        res = torch.zeros(2, dtype=torch.float64, device=inp.device)
+        rc = _lib.lib().come_sgns_pairs_loss(
+            ptr(inp), ptr(out), V, d, ptr(rows_in), ptr(rows_pos), ptr(rows_neg) if n else None,
+            M, n, ptr(per_pair) if return_pairs else None, ptr(res),
+            ptr(res.view(torch.int64)[1:]), stream_handle(inp.device))
+        check(rc, "come_sgns_pairs_loss")
+        total, counted = float(res[0].item()), int(res.view(torch.int64)[1].item())
+    else:
+        total, counted = 0.0, 0
+    return (total, counted, per_pair) if return_pairs else (total, counted)
+
+
 def count_o2_pairs(walks_np, window):
     """Number of pair updates (fast_o2 calls) train_o2 makes over host walks [P, L]."""
     w = np.ascontiguousarray(walks_np, np.int32)
