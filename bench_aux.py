@@ -33,6 +33,13 @@
                   afterwards (same-run spread); then Node2Vec.loss native against torch on 1M
                   edges of the graph taken in random order.  Roofline: (1 + n) rows per pair plus one centre row per centre against
                   HBM (the naive (2 + n) rows per pair beside it).
+  --workload c4_diag  diagonal covariances at C4's shape (1M rows, K=50, d=128) and at d=256: ms per
+                  come_gmm_estep_diag, come_gmm_diag_moments, come_gmm_diag_scatter, whole EM
+                  iteration (its host read included), come_community_grad_diag step and
+                  come_community_loss_diag pass, each beside its full-covariance counterpart timed
+                  in the same run, bit-identity of every diagonal entry across two passes, and each
+                  kernel's roofline: the larger of its compulsory bytes over HBM and its fused
+                  multiply-adds over the fp32 vector peak.
 Each prints one JSON line.  CPU baselines on a bounded sample: O1 the builder's Hogwild C
 restatement of train_o1 (oracle/come_oracle_mt.c; reported beside it as the reference-equivalent
 rate, restatement / its calibrated speed-up over the reference's GIL-bound Node2Vec.train,
@@ -706,6 +713,120 @@ def sgns_loss_bench(args):
         "cpu_baseline": None}))
 
 
+def c4_diag_bench(args):
+    import torch
+    from come_amd import _lib
+    from come_amd import community_embeddings as ce
+    from come_amd import gmm
+    dev = torch.device("cuda", 0)
+    V, K = args.nodes, args.k
+    L, ptr, stream = _lib.lib(), _lib.ptr, _lib.stream_handle(dev)
+    pi_h = np.random.RandomState(3).dirichlet(np.ones(K), V).astype(np.float32)
+    pi = torch.from_numpy(pi_h).to(dev)
+    total = torch.zeros(1, dtype=torch.float64, device=dev)
+    shapes = []
+    for d in sorted({args.dim, 256}):
+        rng = np.random.RandomState(2)
+        mu = (rng.standard_normal((K, d)) * 0.5).astype(np.float32)
+        var = rng.uniform(0.5, 1.5, (K, d)).astype(np.float32)
+        lab = rng.randint(0, K, V)
+        x = torch.from_numpy(mu[lab] + rng.standard_normal((V, d)).astype(np.float32)
+                             * np.sqrt(var[lab])).to(dev)
+        A = rng.standard_normal((K, d, d)) / np.sqrt(d)
+        cov = torch.from_numpy((np.einsum("kij,klj->kil", A, A) + np.eye(d)[None] * 0.5)
+                               .astype(np.float32)).to(dev)
+        mu_t, var_t = torch.from_numpy(mu).to(dev), torch.from_numpy(var).to(dev)
+        w = torch.full((K,), 1.0 / K, dtype=torch.float64, device=dev)
+        # diagonal operands, and the full-covariance ones of the same mixture size
+        ps, mp, ln = (a.float().contiguous() for a in
+                      gmm.diag_estep_params(w, mu_t.double(), var_t.double()))
+        iv = (1.0 / var_t).contiguous()
+        pc_f, mp_f, ln_f = ce.community_loss_params(mu_t, cov)
+        inv_f = torch.linalg.inv(cov).contiguous()
+        resp = gmm.estep_diag(x, ps, mp, ln)[0]
+        gd = gmm.GaussianMixture(K, covariance_type="diag", reg_covar=1e-6)
+        gd._n_total = V
+        gd._set_params(w, mu_t.double(), var_t.double())
+        gf = gmm.GaussianMixture(K, reg_covar=1e-6)
+        gf._n_total = V
+        gf._set_params(w, mu_t.double(), cov.double())
+
+        def em_iter(g):
+            r, lse = g._estep(x)
+            info = g._m_step_params(x, r)
+            return torch.stack([lse.double().sum(), (info != 0).any().double()]).cpu()
+
+        def loss_diag():
+            _lib.check(L.come_community_loss_diag(ptr(x), V, d, ptr(pi), ptr(ps), ptr(mp), ptr(ln),
+                                                  K, None, ptr(total), stream), "loss_diag")
+
+        def loss_full():
+            _lib.check(L.come_community_loss(ptr(x), V, d, ptr(pi), ptr(pc_f), ptr(mp_f), ptr(ln_f),
+                                             K, None, ptr(total), stream), "loss")
+
+        xg = x.clone()
+        pairs = {
+            "estep": (lambda: gmm.estep_diag(x, ps, mp, ln), lambda: gmm.estep(x, pc_f, mp_f, ln_f)),
+            "moments": (lambda: gmm.diag_moments(x, resp),
+                        lambda: (gmm.resp_sum(resp), gmm.resp_t_x(resp, x))),
+            "scatter": (lambda: gmm.diag_scatter(x, resp, mu_t), lambda: gmm.scatter(x, resp, mu_t)),
+            "em_iteration": (lambda: em_iter(gd), lambda: em_iter(gf)),
+            "community_step": (lambda: ce.community_grad_diag(xg, pi, mu_t, iv, 0.1, args.lr, 1),
+                               lambda: ce.community_grad(xg, pi, mu_t, inv_f, 0.1, args.lr, 1)),
+            "loss": (loss_diag, loss_full),
+        }
+        ms = {}
+        for name, (fd, ff) in pairs.items():
+            kd = timed(fd, args.steps, args.warmup)[1]
+            kf = timed(ff, max(2, args.steps // 2), 1)[1]
+            ms[name] = {"diag_ms": float(np.mean(kd)), "diag_ms_min": float(np.min(kd)),
+                        "full_ms": float(np.mean(kf)), "full_ms_min": float(np.min(kf)),
+                        "full_over_diag": float(np.mean(kf) / np.mean(kd))}
+            log("d=%d %s: diag %.3f ms, full %.3f ms" % (d, name, ms[name]["diag_ms"],
+                                                        ms[name]["full_ms"]))
+        # bit-identity across two passes of every diagonal entry
+        def once():
+            r, lse = gmm.estep_diag(x, ps, mp, ln)
+            nk, sx = gmm.diag_moments(x, resp)
+            ssq = gmm.diag_scatter(x, resp, mu_t)
+            y = x.clone()
+            ce.community_grad_diag(y, pi, mu_t, iv, 0.1, args.lr, 2)
+            loss_diag()
+            return r, lse, nk, sx, ssq, y, total.clone()
+        a, b = once(), once()
+        same = all(torch.equal(u, v) for u, v in zip(a, b))
+        # roofline: the larger of compulsory bytes / HBM and fused multiply-adds (2 flop) / the fp32
+        # peak, which the vector unit and the fp32 MFMA (the moments' unit) share; the timings are
+        # taken around the Python wrappers, allocations included, so frac is of wrapper time
+        el = float(V) * K * d
+        xb, rb = 4.0 * V * d, 4.0 * V * K
+        model = {"estep": (xb + rb + 4.0 * V, 2 * el), "moments": (xb + rb, el),
+                 "scatter": (xb + rb, 2 * el), "community_step": (2 * xb + rb, 2 * el),
+                 "loss": (xb + rb, 2 * el)}
+        roof = {}
+        for name, (nbytes, fma) in model.items():
+            t_mem, t_valu = nbytes / (HBM_PEAK_GBS * 1e6), 2 * fma / (F32_MFMA_PEAK_TFLOPS * 1e9)
+            bound = max(t_mem, t_valu)
+            roof[name] = {"bytes": nbytes, "fma": fma, "hbm_ms": t_mem, "valu_ms": t_valu,
+                          "bound": "hbm" if t_mem >= t_valu else "fp32", "bound_ms": bound,
+                          "frac": bound / ms[name]["diag_ms"]}
+        shapes.append({"V": V, "K": K, "d": d, "ms": ms, "roofline": roof,
+                       "bit_identical_two_passes": bool(same),
+                       "chunks": gmm.diag_plan(V, d, K, torch.cuda.get_device_properties(dev)
+                                               .multi_processor_count)})
+        del x, xg, cov, pc_f, inv_f, resp, gd, gf, a, b
+        torch.cuda.empty_cache()
+    first = shapes[0]
+    print(json.dumps({
+        "metric": "diagonal-covariance EM iteration, ms, V=%d K=%d d=%d" % (V, K, first["d"]),
+        "value": first["ms"]["em_iteration"]["diag_ms"], "unit": "ms", "n_gpus": 1,
+        "steps": args.steps, "warmup": args.warmup, "higher_is_better": False, "dtype": "f32",
+        "data": "synthetic (blobs with per-feature variances in [0.5, 1.5], seed 2 / 3)",
+        "config": {"workload": "diagonal-covariance kernels beside their full-covariance "
+                               "counterparts, V=%d K=%d, d in %s" % (V, K, [s_["d"] for s_ in shapes])},
+        "shapes": shapes, "cpu_baseline": None}))
+
+
 def blas_threads():
     """Threads of the BLAS pool numpy / scipy / sklearn run on in this process (threadpoolctl),
     None if it cannot tell."""
@@ -719,7 +840,7 @@ def blas_threads():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["c2", "c4", "walks", "kmeans", "community_loss", "sgns_loss"], required=True)
+    ap.add_argument("--workload", choices=["c2", "c4", "walks", "kmeans", "community_loss", "sgns_loss", "c4_diag"], required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dim", type=int, default=128)
@@ -749,7 +870,8 @@ def main():
             k, v = kv.split("=")
             _lib.set_option(k, int(v))
     {"c2": c2, "c4": c4, "walks": walks, "kmeans": kmeans_bench,
-     "community_loss": community_loss_bench, "sgns_loss": sgns_loss_bench}[args.workload](args)
+     "community_loss": community_loss_bench, "sgns_loss": sgns_loss_bench,
+     "c4_diag": c4_diag_bench}[args.workload](args)
 
 
 if __name__ == "__main__":

@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-/* ABI 5, additive: come_sgns_o2_loss, come_sgns_pairs_loss and their CPU twins (the SGNS
+/* ABI 5, additive: come_gmm_estep_diag, come_gmm_diag_scratch, come_gmm_diag_moments,
+ * come_gmm_diag_scatter, come_community_grad_diag and come_community_loss_diag (diagonal
+ * covariances: the GMM EM, the community step and the community loss for covariance_type='diag').
+ * ABI 5, additive: come_sgns_o2_loss, come_sgns_pairs_loss and their CPU twins (the SGNS
  * objectives O2 / O1 evaluated natively; read-only on the tables).
  * ABI 5, additive: come_kmeans_pp_scratch, come_kmeans_pp_step, come_kmeans_pp_pick and
  * come_kmeans_pp_sample (the greedy k-means++ seeding of come_amd.kmeans).
@@ -254,6 +257,53 @@ int come_gmm_params(const double *scatter, const double *nk, const double *means
                     const double *weights, int K, int d, double reg_covar, double *cov_out,
                     double *prec_chol_out, float *e_prec_chol, float *e_mu_prec,
                     float *e_log_norm, int *info, void *stream);
+
+/* ---- Diagonal covariances (sklearn covariance_type='diag'): Sigma_k = diag(var_k) ----
+ * The same steps as above with d parameters per component instead of d (d + 1) / 2: fp32 VALU
+ * streams over one read of x, for every 1 <= d <= 512 and 1 <= K <= 4096 alike.  All tables are
+ * device fp32, row-major, and need 4-byte alignment only.  No float or double atomics: every
+ * output is bit-identical from run to run.  Asynchronous on `stream`.
+ * Component operands: prec_sqrt [K x d] = 1 / sqrt(var) (sklearn's precisions_cholesky_),
+ * mu_prec [K x d] = mu * prec_sqrt, log_norm [K] = log w_k + sum_j log prec_sqrt[k][j] - d/2
+ * log(2 pi) (without log w_k for the loss); the log-density of (row i, component k) is
+ * log_norm[k] - 1/2 sum_j (x[i][j] prec_sqrt[k][j] - mu_prec[k][j])^2.
+ *
+ * come_gmm_estep_diag: resp_out [V x K] and lse_out [V] as come_gmm_estep defines them; resp_out
+ * may be NULL (lse_out only, bitwise the same).  log_norm[k] = -inf: responsibility exactly 0,
+ * nothing added to lse_out.  V = 0 is a no-op.
+ *
+ * come_gmm_diag_scratch (host): the row chunking of the two M-step passes for a device with `cus`
+ * compute units (<= 0: 256): chunks_out >= 1 with chunks * (K d + K) * 4 <= 128 MB, the size in
+ * bytes of their `scratch` (unused when chunks == 1), and rows_per_chunk_out = ceil(V / chunks),
+ * an upper bound on the rows summed in fp32 before the float64 reduction.
+ *
+ * come_gmm_diag_moments: nk_out [K] = sum_i resp[i][k] and sx_out [K x d] = sum_i resp[i][k]
+ * x[i][j] (device float64); per-chunk fp32 partials reduced in chunk order in float64.
+ *
+ * come_gmm_diag_scatter: ssq_out [K x d] = sum_i resp[i][k] (x[i][j] - means[k][j])^2 (device
+ * float64; means [K x d] fp32), centred as come_gmm_scatter is; chunking as the moments.
+ *
+ * come_community_grad_diag: come_community_grad with inv_cov[k] = diag(inv_var[k]), inv_var
+ * [K x d]: x[i][j] -= lr * clip((beta / K) sum_k pi[i][k] inv_var[k][j] (x[i][j] - mu[k][j]),
+ * +-5), `iters` times in place.  pi is used as given.
+ *
+ * come_community_loss_diag: come_community_loss's contract (row_out [V] or NULL, loss_out one
+ * device double, the total independent of row_out, V = 0 a no-op that leaves loss_out unwritten). */
+int come_gmm_estep_diag(const float *x, int64_t V, int d, const float *prec_sqrt,
+                        const float *mu_prec, const float *log_norm, int K, float *resp_out,
+                        float *lse_out, void *stream);
+int come_gmm_diag_scratch(int64_t V, int d, int K, int cus, int *chunks_out,
+                          int *rows_per_chunk_out);
+int come_gmm_diag_moments(const float *x, int64_t V, int d, const float *resp, int K, int chunks,
+                          void *scratch, double *nk_out, double *sx_out, void *stream);
+int come_gmm_diag_scatter(const float *x, int64_t V, int d, const float *resp, const float *means,
+                          int K, int chunks, void *scratch, double *ssq_out, void *stream);
+int come_community_grad_diag(float *x, int64_t V, int d, const float *pi, const float *mu,
+                             const float *inv_var, int K, float beta, float lr, int iters,
+                             void *stream);
+int come_community_loss_diag(const float *x, int64_t V, int d, const float *pi,
+                             const float *prec_sqrt, const float *mu_prec, const float *log_norm,
+                             int K, float *row_out, double *loss_out, void *stream);
 
 /* ---- k-means (Lloyd): the GMM's initialisation (sklearn KMeans inside GaussianMixture, reference
  * community_embeddings.py:27) and come_amd.kmeans.KMeans ----

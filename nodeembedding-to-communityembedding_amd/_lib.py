@@ -35,7 +35,9 @@ SYMBOLS = ("come_abi_version", "come_last_error", "come_init", "come_exp_table",
            "come_kmeans_assign", "come_kmeans_update", "come_kmeans_pp_scratch",
            "come_kmeans_pp_step", "come_kmeans_pp_pick", "come_kmeans_pp_sample",
            "come_community_loss", "come_cpu_community_loss", "come_sgns_o2_loss",
-           "come_sgns_pairs_loss", "come_cpu_sgns_o2_loss", "come_cpu_sgns_pairs_loss")
+           "come_sgns_pairs_loss", "come_cpu_sgns_o2_loss", "come_cpu_sgns_pairs_loss",
+           "come_gmm_estep_diag", "come_gmm_diag_scratch", "come_gmm_diag_moments",
+           "come_gmm_diag_scatter", "come_community_grad_diag", "come_community_loss_diag")
 
 OPTION_FIELDS = ("o2_kernel", "o2_blocks_per_cu", "o2_waves_per_block",
                  "o2_static", "rows_per_wave", "o1_rows_per_wave",
@@ -109,6 +111,12 @@ def lib():
     L.come_gmm_estep.argtypes = [P, i64, i32, P, P, P, i32, P, P, P]
     L.come_gmm_scatter.argtypes = [P, i64, i32, P, P, i32, i32, P, P, P]
     L.come_gmm_params.argtypes = [P, P, P, P, i32, i32, f64, P, P, P, P, P, P, P]
+    L.come_gmm_estep_diag.argtypes = [P, i64, i32, P, P, P, i32, P, P, P]
+    L.come_gmm_diag_scratch.argtypes = [i64, i32, i32, i32, P, P]
+    L.come_gmm_diag_moments.argtypes = [P, i64, i32, P, i32, i32, P, P, P, P]
+    L.come_gmm_diag_scatter.argtypes = [P, i64, i32, P, P, i32, i32, P, P, P]
+    L.come_community_grad_diag.argtypes = [P, i64, i32, P, P, P, i32, f32, f32, i32, P]
+    L.come_community_loss_diag.argtypes = [P, i64, i32, P, P, P, P, i32, P, P, P]
     L.come_kmeans_scratch.argtypes = [i64, i32, i32, i32, P, P]
     L.come_kmeans_lloyd.argtypes = [P, i64, i32, P, i32, i32, P, P, P, P, P, P, P]
     L.come_kmeans_assign.argtypes = [P, i64, i32, P, i32, P, P, P]

@@ -1,7 +1,11 @@
 """Community embedding trainer -- reference: ADSCModel/community_embeddings.py.
 
 ``Community2Vec(model, lr, reg_covar, gmm_backend="gpu", kmeans_backend='torch',
-kmeans_seeding='torch')`` (``kmeans_backend='native'``: the mixture's k-means initialisation on
+kmeans_seeding='torch', covariance_type='full')`` (``covariance_type='diag'``: diagonal
+covariances for both backends -- covariance_mat and inv_covariance_mat are then [K, d], and
+``train``, ``loss`` and ``responsibilities`` run the diagonal kernels, come_community_grad_diag,
+come_community_loss_diag and come_gmm_estep_diag, dispatching on the stored matrices' dim();
+``kmeans_backend='native'``: the mixture's k-means initialisation on
 come_amd.kmeans; ``kmeans_seeding='native'``: its k-means++ seeding in libcome.so too):
   * ``fit(model)`` (:20-37): fits a GaussianMixture(n_components=k, covariance_type='full',
     n_init=10, reg_covar) -- by default the GPU EM of come_amd.gmm (MFMA E-step and M-step
@@ -73,6 +77,60 @@ def community_grad(x, pi, mu, inv_cov, beta, lr, iters):
     check(rc, "come_community_grad")
 
 
+def gmm_resp_params_diag(weights, means, precisions_cholesky, device):
+    """gmm_resp_params for covariance_type='diag' (precisions_cholesky [K, d] = 1 / sqrt(var)):
+    what come_gmm_estep_diag consumes, derived in float64 and handed over as fp32."""
+    import math
+
+    import torch
+    pc = torch.from_numpy(np.asarray(precisions_cholesky, np.float64))
+    mu = torch.from_numpy(np.asarray(means, np.float64))
+    w = torch.from_numpy(np.asarray(weights, np.float64))
+    ln = torch.log(w) + torch.log(pc).sum(-1) - 0.5 * mu.shape[1] * math.log(2 * math.pi)
+    return tuple(a.float().contiguous().to(device) for a in (pc, mu * pc, ln))
+
+
+def community_grad_diag(x, pi, mu, inv_var, beta, lr, iters):
+    """In-place community gradient steps on all rows of x (CUDA fp32 [V, d]) for diagonal
+    covariances: inv_var [K, d]."""
+    V, d = x.shape
+    K = pi.shape[1]
+    rc = _lib.lib().come_community_grad_diag(ptr(x), V, d, ptr(pi), ptr(mu), ptr(inv_var), K,
+                                             float(beta), float(lr), int(iters),
+                                             stream_handle(x.device))
+    check(rc, "come_community_grad_diag")
+
+
+def community_loss_diag(x, pi, mu, var, return_rows=False):
+    """community_loss for diagonal covariances var [K, d]: the signed total sum_i sum_k pi[i, k]
+    log N(x_i; mu[k], diag(var[k])) as a Python float, or ``(total, rows)``.  The operands are
+    derived in float64 on the device; a variance that is not positive raises ValueError."""
+    import math
+
+    import torch
+    V, d = x.shape
+    K = mu.shape[0]
+    rows = torch.zeros((V,), dtype=torch.float32, device=x.device) if return_rows else None
+    if V == 0:
+        return (0.0, rows) if return_rows else 0.0
+    var64 = var.double()
+    if bool((~(var64 > 0)).any()):
+        raise ValueError("community_loss_diag: variance of component %d is not positive"
+                         % int(torch.nonzero((~(var64 > 0)).any(1))[0]))
+    pc = 1.0 / torch.sqrt(var64)
+    mp = (mu.double() * pc).float().contiguous()
+    ln = (torch.log(pc).sum(-1) - 0.5 * d * math.log(2 * math.pi)).float().contiguous()
+    pc = pc.float().contiguous()
+    x, pi = x.contiguous(), pi.contiguous()
+    total = torch.zeros((1,), dtype=torch.float64, device=x.device)
+    rc = _lib.lib().come_community_loss_diag(ptr(x), V, d, ptr(pi), ptr(pc), ptr(mp), ptr(ln), K,
+                                             ptr(rows) if return_rows else None, ptr(total),
+                                             stream_handle(x.device))
+    check(rc, "come_community_loss_diag")
+    total = float(total.item())
+    return (total, rows) if return_rows else total
+
+
 def community_loss_params(mu, cov):
     """What come_community_loss consumes, derived in float64 on the device and handed over as
     fp32: (prec_chol, mu_prec, log_norm) with prec_chol[k] = P_k, the upper precision Cholesky
@@ -129,7 +187,11 @@ def community_loss(x, pi, mu, cov, return_rows=False):
 
 class Community2Vec(object):
     def __init__(self, model, lr, reg_covar=0, gmm_backend="gpu", distributed=False,
-                 group=None, kmeans_backend='torch', kmeans_seeding='torch'):
+                 group=None, kmeans_backend='torch', kmeans_seeding='torch',
+                 covariance_type='full'):
+        if covariance_type not in ('full', 'diag'):
+            raise NotImplementedError("covariance_type must be 'full' or 'diag'")
+        self.covariance_type = covariance_type
         self.lr = lr
         self.gmm_backend = gmm_backend
         self.distributed = bool(distributed)
@@ -137,7 +199,7 @@ class Community2Vec(object):
         if gmm_backend == "gpu":
             from .gmm import GaussianMixture
             self.g_mixture = GaussianMixture(n_components=model.k, reg_covar=reg_covar,
-                                             covariance_type='full', n_init=10,
+                                             covariance_type=covariance_type, n_init=10,
                                              distributed=distributed, group=group,
                                              kmeans_backend=kmeans_backend,
                                              kmeans_seeding=kmeans_seeding)
@@ -146,7 +208,8 @@ class Community2Vec(object):
                 raise ValueError("distributed=True needs gmm_backend='gpu'")
             from sklearn import mixture
             self.g_mixture = mixture.GaussianMixture(n_components=model.k, reg_covar=reg_covar,
-                                                     covariance_type='full', n_init=10)
+                                                     covariance_type=covariance_type,
+                                                     n_init=10)
         else:
             raise ValueError("gmm_backend must be 'gpu' or 'sklearn'")
 
@@ -167,20 +230,30 @@ class Community2Vec(object):
         cov32 = torch.from_numpy(self.g_mixture.covariances_.astype(np.float32)).to(dev)
         model.centroid = torch.from_numpy(self.g_mixture.means_.astype(np.float32)).to(dev)
         model.covariance_mat = cov32
-        model.inv_covariance_mat = torch.linalg.inv(cov32).contiguous()  # :36, fp32 inverse
+        if cov32.dim() == 2:  # 'diag': [K, d]
+            model.inv_covariance_mat = (1.0 / cov32).contiguous()
+        else:
+            model.inv_covariance_mat = torch.linalg.inv(cov32).contiguous()  # :36, fp32 inverse
         model.pi = self.responsibilities(model)
 
     def responsibilities(self, model):
         import torch
         g = self.g_mixture
         x = model.node_embedding
-        pc, mp, ln = gmm_resp_params(g.weights_, g.means_, g.precisions_cholesky_, x.device)
+        if np.ndim(g.precisions_cholesky_) == 2:  # 'diag'
+            from .gmm import estep_diag
+            pc, mp, ln = gmm_resp_params_diag(g.weights_, g.means_, g.precisions_cholesky_,
+                                              x.device)
+            resp_of = lambda rows: estep_diag(rows.contiguous(), pc, mp, ln)[0]  # noqa: E731
+        else:
+            pc, mp, ln = gmm_resp_params(g.weights_, g.means_, g.precisions_cholesky_, x.device)
+            resp_of = lambda rows: gmm_resp(rows, pc, mp, ln)  # noqa: E731
         if not self.distributed:
-            return gmm_resp(x, pc, mp, ln)
+            return resp_of(x)
         V = x.shape[0]
         lo, hi = self._shard(V)
         pi = torch.empty((V, pc.shape[0]), dtype=torch.float32, device=x.device)
-        pi[lo:hi] = gmm_resp(x[lo:hi], pc, mp, ln)
+        pi[lo:hi] = resp_of(x[lo:hi])
         return all_gather_rows(pi, self.group)
 
     def loss(self, nodes, model, beta, chunksize=150):
@@ -205,7 +278,8 @@ class Community2Vec(object):
         lo, hi = self._shard(len(rows))
         total = 0.0
         if hi > lo:  # a row block of a C-contiguous table is itself contiguous
-            total = community_loss(x[lo:hi], pi[lo:hi], model.centroid, model.covariance_mat)
+            loss_of = community_loss_diag if model.covariance_mat.dim() == 2 else community_loss
+            total = loss_of(x[lo:hi], pi[lo:hi], model.centroid, model.covariance_mat)
         if self.distributed and world_of(self.group)[1] > 1:
             t = torch.tensor([total], dtype=torch.float64, device=x.device)
             all_reduce_sum([t], self.group)
@@ -225,12 +299,14 @@ class Community2Vec(object):
         if (rows < 0).any():
             raise KeyError(int(ids[np.argmax(rows < 0)]))
         x = model.node_embedding
+        # ([K, d] inverse variances: fit's covariance_type='diag'; train reads no covariance_mat)
+        grad = community_grad_diag if model.inv_covariance_mat.dim() == 2 else community_grad
         chunksize = max(1, int(chunksize))
         if len(rows) == model.vocab_size and (np.sort(rows) == np.arange(len(rows))).all():
             lo, hi = self._shard(x.shape[0])
             if hi > lo:  # a row block of a C-contiguous table is itself contiguous
-                community_grad(x[lo:hi], model.pi[lo:hi], model.centroid,
-                               model.inv_covariance_mat, beta, self.lr, iter)
+                grad(x[lo:hi], model.pi[lo:hi], model.centroid, model.inv_covariance_mat, beta,
+                     self.lr, iter)
             if self.distributed:
                 all_gather_rows(x, self.group)
             return
@@ -246,8 +322,8 @@ class Community2Vec(object):
         pi = pi.contiguous()
         lo, hi = self._shard(len(uniq))
         if hi > lo:
-            community_grad(sub[lo:hi], pi[lo:hi], model.centroid, model.inv_covariance_mat, beta,
-                           self.lr, iter)
+            grad(sub[lo:hi], pi[lo:hi], model.centroid, model.inv_covariance_mat, beta, self.lr,
+                 iter)
         if self.distributed:
             all_gather_rows(sub, self.group)
         x.index_copy_(0, idx, sub)

@@ -1,9 +1,9 @@
-"""Full-covariance Gaussian mixture EM on the GPU -- replaces the reference's
+"""Gaussian mixture EM on the GPU (full or diagonal covariances) -- replaces the reference's
 ``sklearn.mixture.GaussianMixture(n_components=k, covariance_type='full', n_init=10,
 reg_covar=...).fit(X)`` (ADSCModel/community_embeddings.py:18,27).
 
 Same estimator surface as sklearn for the parts the reference uses: constructor arguments
-(n_components, covariance_type='full' only, tol, reg_covar, max_iter, n_init, init_params=
+(n_components, covariance_type='full' | 'diag', tol, reg_covar, max_iter, n_init, init_params=
 'kmeans' | 'random', weights_init, means_init, precisions_init, random_state), ``fit``,
 ``predict_proba``, ``predict``, ``score``, and the fitted attributes ``weights_``, ``means_``,
 ``covariances_``, ``precisions_cholesky_``, ``precisions_``, ``converged_``, ``n_iter_``,
@@ -21,6 +21,15 @@ Parity: with fixed initial parameters the iterations match sklearn's within fp32
 (tests/test_gpu_gmm.py).  The default k-means initialisation (k-means++ seeding then Lloyd,
 sklearn's KMeans(n_init=1) semantics) draws from its own device generator, so -- like the
 reference, whose GaussianMixture is unseeded -- which local optimum a fit reaches is not pinned.
+
+``covariance_type='diag'`` (sklearn's semantics: covariances_, precisions_cholesky_ = 1 / sqrt(cov)
+and precisions_ of shape [K, d], precisions_init [K, d]) runs the same loop on the diagonal
+kernels of libcome.so, for every d <= 512 and n_components <= 4096: come_gmm_estep_diag, and an
+M-step of two passes over the rows, come_gmm_diag_moments (nk, resp^T X) and come_gmm_diag_scatter
+(the centred sum_i r_ik (x_ij - mu_kj)^2), both in float64 from per-chunk fp32 sums.  The
+parameter step between them is [K, d] float64 elementwise work in torch (no Cholesky); the
+"some variance <= 0" status is read beside the lower bound, one host read per iteration.
+Distributed, nk and resp^T X are all-reduced before the means and the K d scatter sums after.
 
 Multi-GPU (``distributed=True``): every rank passes ITS shard of the rows to
 ``fit``; the E-step stays local and the M-step all-reduces the sufficient statistics over the
@@ -65,6 +74,85 @@ def estep(X, prec_chol, mu_prec, log_norm):
                                     ptr(resp), ptr(lse), stream_handle(X.device)),
           "come_gmm_estep")
     return resp, lse
+
+
+def estep_diag(X, prec_sqrt, mu_prec, log_norm, want_resp=True):
+    """(resp [V, K] or None, lse [V]) of a diagonal-covariance mixture for device fp32 X:
+    prec_sqrt [K, d] = 1 / sqrt(var), mu_prec = mu * prec_sqrt, log_norm [K] = log w + sum_j log
+    prec_sqrt - d/2 log(2 pi).  ``want_resp=False`` passes resp_out = NULL (lse only)."""
+    import torch
+    V, d = X.shape
+    K = prec_sqrt.shape[0]
+    resp = torch.empty((V, K), dtype=torch.float32, device=X.device) if want_resp else None
+    lse = torch.empty((V,), dtype=torch.float32, device=X.device)
+    check(_lib.lib().come_gmm_estep_diag(ptr(X), V, d, ptr(prec_sqrt), ptr(mu_prec),
+                                         ptr(log_norm), K, ptr(resp) if want_resp else None,
+                                         ptr(lse), stream_handle(X.device)),
+          "come_gmm_estep_diag")
+    return resp, lse
+
+
+def diag_plan(V, d, K, cus):
+    """(chunks, rows_per_chunk) of the diagonal M-step passes: come_gmm_diag_scratch (host)."""
+    import ctypes
+    c, r = ctypes.c_int(0), ctypes.c_int(0)
+    check(_lib.lib().come_gmm_diag_scratch(int(V), int(d), int(K), int(cus), ctypes.byref(c),
+                                           ctypes.byref(r)), "come_gmm_diag_scratch")
+    return c.value, r.value
+
+
+def _diag_chunks(X, K, chunks):
+    import torch
+    V, d = X.shape
+    if chunks is None:
+        cus = torch.cuda.get_device_properties(X.device).multi_processor_count
+        chunks = diag_plan(V, d, K, cus)[0]
+    chunks = int(chunks)
+    scratch = torch.empty((chunks * (K * d + K),) if chunks > 1 else (1,), dtype=torch.float32,
+                          device=X.device)
+    return chunks, scratch
+
+
+def diag_moments(X, resp, chunks=None):
+    """(nk [K], sx [K, d]) device float64: sum_i resp[i, k] and sum_i resp[i, k] x[i, j]."""
+    import torch
+    V, d = X.shape
+    K = resp.shape[1]
+    chunks, scratch = _diag_chunks(X, K, chunks)
+    nk = torch.empty((K,), dtype=torch.float64, device=X.device)
+    sx = torch.empty((K, d), dtype=torch.float64, device=X.device)
+    resp = resp.contiguous()
+    check(_lib.lib().come_gmm_diag_moments(ptr(X), V, d, ptr(resp), K, chunks, ptr(scratch),
+                                           ptr(nk), ptr(sx), stream_handle(X.device)),
+          "come_gmm_diag_moments")
+    return nk, sx
+
+
+def diag_scatter(X, resp, means, chunks=None):
+    """[K, d] device float64: sum_i resp[i, k] (x[i, j] - means[k, j])^2 (means cast to fp32)."""
+    import torch
+    V, d = X.shape
+    K = resp.shape[1]
+    chunks, scratch = _diag_chunks(X, K, chunks)
+    out = torch.empty((K, d), dtype=torch.float64, device=X.device)
+    means = means.to(torch.float32).contiguous()
+    resp = resp.contiguous()
+    check(_lib.lib().come_gmm_diag_scatter(ptr(X), V, d, ptr(resp), ptr(means), K, chunks,
+                                           ptr(scratch), ptr(out), stream_handle(X.device)),
+          "come_gmm_diag_scatter")
+    return out
+
+
+def diag_estep_params(weights, means, cov):
+    """What the diagonal E-step consumes, in float64 (torch tensors on any device): (prec_sqrt,
+    mu_prec, log_norm) = (1 / sqrt(cov), means * prec_sqrt, log weights + sum_j log prec_sqrt -
+    d/2 log(2 pi)) -- sklearn's _compute_precision_cholesky(cov, 'diag') and the constants of
+    _estimate_log_gaussian_prob."""
+    import torch
+    d = means.shape[1]
+    pc = 1.0 / torch.sqrt(cov)
+    log_norm = torch.log(weights) + torch.log(pc).sum(-1) - 0.5 * d * math.log(2 * math.pi)
+    return pc, means * pc, log_norm
 
 
 def resp_t_x(resp, X, chunks=256):
@@ -178,9 +266,9 @@ class GaussianMixture(object):
             raise ValueError("kmeans_seeding must be 'torch' or 'native'")
         if kmeans_seeding == 'native' and kmeans_backend != 'native':
             raise ValueError("kmeans_seeding='native' needs kmeans_backend='native'")
-        if covariance_type != 'full':
-            raise NotImplementedError("only covariance_type='full' (the reference's) is "
-                                      "implemented")
+        if covariance_type not in ('full', 'diag'):
+            raise NotImplementedError("only covariance_type='full' (the reference's) and 'diag' "
+                                      "are implemented")
         if init_params not in ('kmeans', 'random'):
             raise ValueError("init_params must be 'kmeans' or 'random'")
         self.n_components = int(n_components)
@@ -223,6 +311,8 @@ class GaussianMixture(object):
         import torch
         V, d = X.shape
         world = self._rank_world()[1]
+        if self.covariance_type == 'diag':
+            return self._m_step_diag(X, resp)
         nk = resp_sum(resp)
         sx = resp_t_x(resp, X)
         if world > 1:
@@ -236,6 +326,22 @@ class GaussianMixture(object):
         cov += self.reg_covar * torch.eye(d, dtype=torch.float64, device=X.device)
         return nk / (self._n_total if world > 1 else V), means, cov
 
+    def _m_step_diag(self, X, resp):
+        """sklearn _estimate_gaussian_parameters ('diag'): weights, means, covariances [K, d] =
+        ssq / nk + reg_covar, with the centred sum of squares about the fp32-rounded means."""
+        V = X.shape[0]
+        world = self._rank_world()[1]
+        nk, sx = diag_moments(X, resp)
+        if world > 1:
+            all_reduce_sum([nk, sx], self.group)
+        nk = nk + 10 * np.finfo(np.float64).eps
+        means = sx / nk[:, None]
+        ssq = diag_scatter(X, resp, means)
+        if world > 1:
+            all_reduce_sum([ssq], self.group)
+        cov = ssq / nk[:, None] + self.reg_covar
+        return nk / (self._n_total if world > 1 else V), means, cov
+
     def _m_step_params(self, X, resp):
         """One M-step and the E-step inputs it implies: _m_step + _set_params with everything
         after the scatter in one launch (come_gmm_params: cov, Cholesky, prec_chol = L^-T and the
@@ -245,6 +351,13 @@ class GaussianMixture(object):
         import torch
         V, d = X.shape
         K = resp.shape[1]
+        if self.covariance_type == 'diag':
+            w, mu, cov = self._m_step_diag(X, resp)
+            bad = (~(cov > 0)).any(1).to(torch.int32)  # (a NaN variance is ill-defined too)
+            self._w, self._mu, self._cov = w, mu, cov
+            self._pc = 1.0 / torch.sqrt(torch.where(cov > 0, cov, torch.ones_like(cov)))
+            self._prepare_estep()
+            return bad
         if d > 128:
             self._set_params(*self._m_step(X, resp))
             return torch.zeros(K, dtype=torch.int32, device=X.device)
@@ -275,6 +388,12 @@ class GaussianMixture(object):
     def _set_params(self, weights, means, cov):
         import torch
         d = means.shape[1]
+        if self.covariance_type == 'diag':
+            if bool((~(cov > 0)).any()):
+                self._raise_ill_defined()
+            self._w, self._mu, self._cov, self._pc = weights, means, cov, 1.0 / torch.sqrt(cov)
+            self._prepare_estep()
+            return
         chol, info = torch.linalg.cholesky_ex(cov)
         if bool((info != 0).any()):
             raise ValueError("Fitting the mixture model failed because some components have "
@@ -288,6 +407,11 @@ class GaussianMixture(object):
 
     def _set_params_from_precisions(self, weights, means, precisions):
         import torch
+        if self.covariance_type == 'diag':  # sklearn: precisions_cholesky_ = sqrt(precisions_init)
+            self._w, self._mu, self._pc = weights, means, torch.sqrt(precisions)
+            self._cov = 1.0 / precisions
+            self._prepare_estep()
+            return
         pchol = torch.linalg.cholesky(precisions)  # sklearn: cholesky of the precision, lower
         self._w, self._mu, self._pc = weights, means, pchol.contiguous()
         self._cov = torch.cholesky_inverse(pchol)
@@ -296,6 +420,12 @@ class GaussianMixture(object):
     def _prepare_estep(self):
         import torch
         d = self._mu.shape[1]
+        if self.covariance_type == 'diag':
+            ln = torch.log(self._w) + torch.log(self._pc).sum(-1) - 0.5 * d * math.log(2 * math.pi)
+            self._e_pc = self._pc.float().contiguous()
+            self._e_mp = (self._mu * self._pc).float().contiguous()
+            self._e_ln = ln.float().contiguous()
+            return
         log_det = torch.log(torch.diagonal(self._pc, dim1=-2, dim2=-1)).sum(-1)
         self._e_pc = self._pc.float().contiguous()
         self._e_mp = torch.einsum("kd,kde->ke", self._mu, self._pc).float().contiguous()
@@ -417,6 +547,11 @@ class GaussianMixture(object):
         else:
             self._set_params(w, mu, cov)
 
+    def _estep(self, X, want_resp=True):
+        if self.covariance_type == 'diag':
+            return estep_diag(X, self._e_pc, self._e_mp, self._e_ln, want_resp)
+        return estep(X, self._e_pc, self._e_mp, self._e_ln)
+
     # ---- EM ------------------------------------------------------------------------------------
     def fit(self, X, y=None):
         self.fit_predict(X)
@@ -430,7 +565,10 @@ class GaussianMixture(object):
         if self._n_total < self.n_components:
             raise ValueError("Expected n_samples >= n_components but got n_components = %d, "
                              "n_samples = %d" % (self.n_components, self._n_total))
-        if d > 512 or self.n_components > (4096 if d in (64, 128) or d > 128 else 64):
+        if self.covariance_type == 'diag':
+            if d > 512 or self.n_components > 4096:
+                raise ValueError("GPU GaussianMixture supports d <= 512 and n_components <= 4096")
+        elif d > 512 or self.n_components > (4096 if d in (64, 128) or d > 128 else 64):
             raise ValueError("GPU GaussianMixture supports d <= 512 and n_components <= 64 "
                              "(<= 4096 for d = 64, 128 and d > 128)")
         gen = self._generator(X.device)
@@ -442,7 +580,7 @@ class GaussianMixture(object):
             converged, n_iter = False, 0
             for n_iter in range(1, self.max_iter + 1):
                 prev = lb
-                resp, lse = estep(X, self._e_pc, self._e_mp, self._e_ln)
+                resp, lse = self._estep(X)
                 info = self._m_step_params(X, resp)
                 # one host read per iteration: the lower bound and the Cholesky status together
                 lb_info = torch.stack([lse.double().sum(), (info != 0).any().double()]).cpu()
@@ -458,7 +596,7 @@ class GaussianMixture(object):
         self._w, self._mu, self._cov, self._pc, self.n_iter_, self.converged_ = best
         self._prepare_estep()
         self.lower_bound_ = max_lb
-        resp, _ = estep(X, self._e_pc, self._e_mp, self._e_ln)
+        resp, _ = self._estep(X)
         self._export()
         return torch.argmax(resp, 1)
 
@@ -469,12 +607,15 @@ class GaussianMixture(object):
         self.covariances_ = self._cov.cpu().numpy()
         self.precisions_cholesky_ = self._pc.cpu().numpy()
         pc = self._pc
+        if self.covariance_type == 'diag':
+            self.precisions_ = (pc * pc).cpu().numpy()
+            return
         self.precisions_ = torch.matmul(pc, pc.transpose(-1, -2)).cpu().numpy()
 
     # ---- inference ----------------------------------------------------------------------------
     def predict_proba(self, X):
         X = self._prepare_x(X)
-        return estep(X, self._e_pc, self._e_mp, self._e_ln)[0]
+        return self._estep(X)[0]
 
     def predict(self, X):
         import torch
@@ -483,6 +624,6 @@ class GaussianMixture(object):
     def score(self, X, y=None):
         """Mean log-likelihood over all rows (over every rank's shard when distributed)."""
         X = self._prepare_x(X)
-        lse = estep(X, self._e_pc, self._e_mp, self._e_ln)[1]
+        lse = self._estep(X, want_resp=False)[1]
         n = self._global_sum(X.shape[0], X.device)
         return self._global_sum(lse.double().sum(), X.device) / n
