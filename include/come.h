@@ -588,6 +588,33 @@ int come_sgns_o2_ex(float *node, float *ctx, int64_t V, int d, const int32_t *wa
  * and grows with its count (degree), i.e. with how often walks visit it.  Asynchronous. */
 int come_hot_rows(const uint32_t *table, uint64_t T, int64_t V, uint64_t min_count,
                   uint32_t *counts, uint32_t *hot_bits, void *stream);
+/* Quiet rows of the node table, for come_sgns_o2_quiet: quiet_bits (device uint32 [ceil(V / 32)])
+ * bit v set iff row v is not hot (fewer than hot_min_count slots of the table hold v) and
+ *     visitors * share_v <= eps,
+ * share_v = row v's share of walk visits = its degree share, recovered from the table: the slots
+ * holding the value v + id_shift are sized by row v's count^power (the table stores node ids and
+ * the kernels read them as rows, so id_shift = 1 for ids 1..V), hence share_v =
+ * counts[v + id_shift]^(1/power) / sum_u counts[u]^(1/power).  A row whose own count the table
+ * does not hold (v + id_shift outside [0, V)) is not quiet.  visitors = wavefronts in flight *
+ * (2 * window + 1): the product is the expected number of other wavefronts with the row inside
+ * their walk window.  counts: device uint32 [V] scratch; sum: device double [1] scratch.
+ * Plain (unpacked) table only.  Asynchronous. */
+int come_quiet_rows(const uint32_t *table, uint64_t T, int64_t V, double power, int id_shift,
+                    double visitors, double eps, uint64_t hot_min_count, uint32_t *counts,
+                    double *sum, uint32_t *quiet_bits, void *stream);
+/* come_sgns_o2_ex with a quiet-row bitmap (come_quiet_rows), or NULL = come_sgns_o2_ex.  Where
+ * the Hogwild launch runs the streaming kernel with d <= 128, negative <= 5, window <= 5 and
+ * V < 2^30, a quiet input row is read once when a walk position holding it enters the
+ * wavefront's window and written back once when the last such position leaves it (an LDS ring
+ * per wavefront), instead of once per pair; other wavefronts' updates of the row during the
+ * stay are overwritten.  With one wavefront the results are bit-identical to come_sgns_o2_ex.
+ * Every other shape, kernel and mode ignores the bitmap.  Default grid there: 5 four-wave
+ * workgroups per CU (o2_blocks_per_cu = 0). */
+int come_sgns_o2_quiet(float *node, float *ctx, int64_t V, int d, const int32_t *walks, int64_t P,
+                       int L, const uint64_t *seeds, int window, int negative,
+                       const uint32_t *table, uint64_t T, float lr, float alpha, int mode,
+                       const uint32_t *hot_rows, const uint32_t *quiet_rows,
+                       const come_launch_opts *opts, void *stream);
 /* come_sgns_o1 with the contended-row bitmap (Hogwild: an update of a hot endpoint row is a
  * float-atomic delta; NULL = derived from the table, COME_HOT_NONE = none, as come_sgns_o2_ex)
  * and per-call options (opts may be NULL = process-wide). */

@@ -37,7 +37,8 @@ SYMBOLS = ("come_abi_version", "come_last_error", "come_init", "come_exp_table",
            "come_community_loss", "come_cpu_community_loss", "come_sgns_o2_loss",
            "come_sgns_pairs_loss", "come_cpu_sgns_o2_loss", "come_cpu_sgns_pairs_loss",
            "come_gmm_estep_diag", "come_gmm_diag_scratch", "come_gmm_diag_moments",
-           "come_gmm_diag_scatter", "come_community_grad_diag", "come_community_loss_diag")
+           "come_gmm_diag_scatter", "come_community_grad_diag", "come_community_loss_diag",
+           "come_quiet_rows", "come_sgns_o2_quiet")
 
 OPTION_FIELDS = ("o2_kernel", "o2_blocks_per_cu", "o2_waves_per_block",
                  "o2_static", "rows_per_wave", "o1_rows_per_wave",
@@ -133,6 +134,9 @@ def lib():
     L.come_sgns_o2_ex.argtypes = [P, P, i64, i32, P, i64, i32, P, i32, i32, P, u64, f32, f32, i32,
                                   P, P, P]
     L.come_hot_rows.argtypes = [P, u64, i64, u64, P, P, P]
+    L.come_quiet_rows.argtypes = [P, u64, i64, f64, i32, f64, f64, u64, P, P, P, P]
+    L.come_sgns_o2_quiet.argtypes = [P, P, i64, i32, P, i64, i32, P, i32, i32, P, u64, f32, f32,
+                                     i32, P, P, P, P]
     L.come_lcg_table_draws.argtypes = [u64, i64, P, u64, P]
     L.come_delta_flags.argtypes = [P, P, i64, i32, P, P]
     L.come_delta_gather.argtypes = [P, P, P, i64, i32, P, P, P]

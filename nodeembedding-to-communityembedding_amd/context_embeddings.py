@@ -62,7 +62,7 @@ class Context2Vec(object):
     def __init__(self, lr=0.1, window_size=5, workers=1, negative=5, deterministic=False,
                  batch_walks=1 << 20, distributed=False, sync_walks=DEFAULT_SYNC_WALKS,
                  sparse_sync=False, overlap=True, group=None, hot_share=None, launch_opts=None,
-                 combine="touched_mean"):
+                 combine="touched_mean", quiet_eps=None):
         self.lr = float(lr)
         self.workers = workers
         self.negative = negative
@@ -76,6 +76,9 @@ class Context2Vec(object):
         self.group = group
         self.hot_share = hot_share      # None = training_sdg_inner.default_hot_share(d)
         self.launch_opts = launch_opts  # per-call come_launch_opts fields (A/B runs)
+        # rows with at most this many expected concurrent visitors stay on chip over a walk window
+        # (Model.quiet_rows; None = training_sdg_inner.DEFAULT_QUIET_EPS, 0 = off)
+        self.quiet_eps = quiet_eps
         self.combine = combine          # DeltaAllReduce combine rule
         self._exchanges = {}
         if self.distributed and self.deterministic:
@@ -185,6 +188,28 @@ class Context2Vec(object):
                  elapsed, pairs / elapsed if elapsed else 0.0)
         return pairs
 
+    def quiet_rows(self, model, walks):
+        """The quiet-row bitmap for a Hogwild launch of up to `walks` walks on this model's
+        device, or None: the rule counts the wavefronts such a launch keeps in flight (its grid of
+        four-wave workgroups, the max_waves / o2_blocks_per_cu launch options, one walk each).
+        The launcher ignores it where the windowed stream kernel does not run."""
+        import torch
+        eps = tsi.DEFAULT_QUIET_EPS if self.quiet_eps is None else float(self.quiet_eps)
+        dev = model.node_embedding.device
+        if eps <= 0 or dev.type != "cuda" or self.window_size > 5 or self.negative > 5 \
+                or model.layer1_size > 128:
+            return None
+        opts = self.launch_opts or {}
+        bpc = int(opts.get("o2_blocks_per_cu", 0)) or tsi.QUIET_BLOCKS_PER_CU
+        waves = 4 * bpc * torch.cuda.get_device_properties(dev).multi_processor_count
+        if int(opts.get("max_waves", 0)) > 0:
+            waves = min(waves, int(opts["max_waves"]))
+        waves = max(1, min(waves, int(walks), self.batch_walks))
+        # small graphs run the direct kernel (fewer than 32 rows per wavefront in flight)
+        if int(opts.get("o2_kernel", 0)) != 3 and model.vocab_size < 32 * waves:
+            return None
+        return model.quiet_rows(waves, self.window_size, eps, self.hot_share)
+
     def train_rows(self, model, rows, seeds, alpha=1.0, n_batches=None, update_count=None,
                    launch_events=None):
         """The launches (and, distributed, the exchanges) of train() over walk rows already
@@ -199,6 +224,7 @@ class Context2Vec(object):
         dev = model.node_embedding.device
         mode = tsi.MODE_SEQUENTIAL if self.deterministic else tsi.MODE_HOGWILD
         hot = None if self.deterministic else model.hot_rows(self.hot_share)
+        quiet = None if self.deterministic else self.quiet_rows(model, rows.shape[0])
         table = model.negative_table()
         rank, world = self.world()
         ex = self.exchange(model) if world > 1 else None
@@ -224,7 +250,8 @@ class Context2Vec(object):
                     ev[0].record(stream)
                 tsi.sgns_o2(model.node_embedding, model.context_embedding, w, sd,
                             self.window_size, self.negative, table, self.lr, alpha, mode,
-                            opts=self.launch_opts, hot=hot, update_count=update_count)
+                            opts=self.launch_opts, hot=hot, update_count=update_count,
+                            **({} if quiet is None else {"quiet": quiet}))
                 if launch_events is not None:
                     ev[1].record(stream)
                     launch_events.append(ev)

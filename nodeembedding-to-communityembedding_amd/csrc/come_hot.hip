@@ -83,6 +83,50 @@ __global__ void __launch_bounds__(256) k_hot_bits(const uint32_t *__restrict__ c
     }
 }
 
+// ---- "quiet" rows: the node-table rows so rarely visited that a wavefront may hold one for a
+// walk window (the windowed stream kernel's LDS ring).  What makes a hold harmful is another
+// wavefront visiting the row meanwhile, so the rule is on the expected number of such visitors:
+//     visitors x (the row's share of walk visits) <= eps,
+// visitors = wavefronts in flight x (2w + 1) positions each.  The visit share is the degree share,
+// recovered from the table: node id v + id_shift (row v) got count^power / Z of the slots, and the
+// slots hold the *id*, which the kernels use as a row (model.py:97-122) -- so row v's own count
+// sizes the slots of row v + id_shift, and share_v = counts[v + id_shift]^(1/power) / sum_u
+// counts[u]^(1/power).  A row whose count the table does not hold (v + id_shift >= V: the table's
+// clamp folds it into its last value) is not quiet, and neither is a hot row.
+
+// sum[0] += sum_v counts[v]^(1/power)
+__global__ void __launch_bounds__(256) k_quiet_sum(const uint32_t *__restrict__ counts, int64_t V,
+                                                   double inv_power, double *__restrict__ sum) {
+    double s = 0.0;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < V;
+         v += (int64_t)gridDim.x * blockDim.x)
+        s += pow((double)counts[v], inv_power);
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o);
+    if ((threadIdx.x & 63) == 0 && s != 0.0) atomicAdd(sum, s);
+}
+
+// quiet_bits[w] bit b = row 32 w + b is quiet
+__global__ void __launch_bounds__(256) k_quiet_bits(const uint32_t *__restrict__ counts, int64_t V,
+                                                    int id_shift, double inv_power,
+                                                    double visitors, double eps,
+                                                    uint64_t hot_min_count,
+                                                    const double *__restrict__ sum,
+                                                    uint32_t *__restrict__ quiet_bits) {
+    const int64_t words = (V + 31) / 32;
+    const double bound = eps * sum[0] / visitors;  // on counts[.]^(1/power)
+    for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < words;
+         w += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t bits = 0;
+        for (int b = 0; b < 32; ++b) {
+            const int64_t r = 32 * w + b, own = r + id_shift;
+            if (r < V && own >= 0 && own < V && counts[r] < hot_min_count &&
+                pow((double)counts[own], inv_power) <= bound)
+                bits |= 1u << b;
+        }
+        quiet_bits[w] = bits;
+    }
+}
+
 static int hot_rows_impl(int dev, const uint32_t *table, uint64_t T, int packed, int64_t V,
                          uint64_t min_count, uint32_t *counts, uint32_t *hot_bits, void *stream) {
     hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint32_t) * (size_t)V, (hipStream_t)stream);
@@ -133,4 +177,41 @@ extern "C" int come_hot_rows(const uint32_t *table, uint64_t T, int64_t V, uint6
     int rc = ensure_init(&dev);
     if (rc) return rc;
     return hot_rows_impl(dev, table, T, 0, V, min_count, counts, hot_bits, stream);
+}
+
+extern "C" int come_quiet_rows(const uint32_t *table, uint64_t T, int64_t V, double power,
+                               int id_shift, double visitors, double eps, uint64_t hot_min_count,
+                               uint32_t *counts, double *sum, uint32_t *quiet_bits, void *stream) {
+    if (V <= 0 || V > INT32_MAX) return set_error(COME_E_INVALID, "quiet_rows: V out of range");
+    if (!table || !counts || !sum || !quiet_bits || T == 0)
+        return set_error(COME_E_INVALID, "quiet_rows: null pointer or empty table");
+    if (!(power > 0.0) || !(visitors > 0.0) || !(eps >= 0.0))
+        return set_error(COME_E_INVALID, "quiet_rows: power and visitors must be > 0, eps >= 0");
+    int dev = 0;
+    int rc = ensure_init(&dev);
+    if (rc) return rc;
+    hipError_t e = hipMemsetAsync(counts, 0, sizeof(uint32_t) * (size_t)V, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_error(e, "hipMemsetAsync(counts)");
+    e = hipMemsetAsync(sum, 0, sizeof(double), (hipStream_t)stream);
+    if (e != hipSuccess) return hip_error(e, "hipMemsetAsync(sum)");
+    uint64_t blocks = (T + 255) / 256;
+    const uint64_t cap = (uint64_t)num_cus(dev) * 16;
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL(k_table_counts, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                       table, T, V, counts);
+    rc = hip_error(hipGetLastError(), "k_table_counts launch");
+    if (rc) return rc;
+    int64_t vb = (V + 255) / 256;
+    if (vb > 4096) vb = 4096;
+    hipLaunchKernelGGL(k_quiet_sum, dim3((unsigned)vb), dim3(256), 0, (hipStream_t)stream,
+                       (const uint32_t *)counts, V, 1.0 / power, sum);
+    rc = hip_error(hipGetLastError(), "k_quiet_sum launch");
+    if (rc) return rc;
+    const int64_t words = (V + 31) / 32;
+    int64_t wb = (words + 255) / 256;
+    if (wb > 4096) wb = 4096;
+    hipLaunchKernelGGL(k_quiet_bits, dim3((unsigned)wb), dim3(256), 0, (hipStream_t)stream,
+                       (const uint32_t *)counts, V, id_shift, 1.0 / power, visitors, eps,
+                       hot_min_count, (const double *)sum, quiet_bits);
+    return hip_error(hipGetLastError(), "k_quiet_bits launch");
 }

@@ -118,11 +118,11 @@ static bool aligned_for(const void *p, int d) {
     return ((uintptr_t)p % bytes) == 0;
 }
 
-extern "C" int come_sgns_o2_ex(float *node, float *ctx, int64_t V, int d, const int32_t *walks,
-                               int64_t P, int L, const uint64_t *seeds, int window, int negative,
-                               const uint32_t *table, uint64_t T, float lr, float alpha, int mode,
-                               const uint32_t *hot_rows, const come_launch_opts *opts,
-                               void *stream) {
+static int sgns_o2_impl(float *node, float *ctx, int64_t V, int d, const int32_t *walks,
+                        int64_t P, int L, const uint64_t *seeds, int window, int negative,
+                        const uint32_t *table, uint64_t T, float lr, float alpha, int mode,
+                        const uint32_t *hot_rows, const uint32_t *quiet_rows,
+                        const come_launch_opts *opts, void *stream) {
     const come_launch_opts o = opts ? *opts : current_opts();
     int packed = 0, hot_none = 0;
     int rc = check_common(V, d, negative, table, T, mode, packed, hot_none);
@@ -148,7 +148,7 @@ extern "C" int come_sgns_o2_ex(float *node, float *ctx, int64_t V, int d, const 
     O2Args a{node, ctx, walks, seeds, table, V, P, L, d, window, negative, lr, alpha,
              make_fastmod(T), packed, nullptr,
              reinterpret_cast<unsigned long long *>(o.o2_update_count), o.o2_fresh_loads,
-             o.o2_atomic_writeback, mode == COME_MODE_HOGWILD ? hot_rows : nullptr};
+             o.o2_atomic_writeback, mode == COME_MODE_HOGWILD ? hot_rows : nullptr, nullptr};
     int full = 0;
     const KernelSet &ks = kernel_set(d, &full);
     const int mi = maxn_index(negative);
@@ -162,7 +162,11 @@ extern "C" int come_sgns_o2_ex(float *node, float *ctx, int64_t V, int d, const 
         int dev = 0;
         rc = ensure_init(&dev);
         if (rc) return rc;
-        const int bpc = o.o2_blocks_per_cu > 0 ? o.o2_blocks_per_cu : 8;
+        // quiet rows: the windowed instantiation (d <= 128, n <= 5, w <= 5, rows < 2^30), whose
+        // LDS ring lets five workgroups share a CU; any other shape ignores the bitmap
+        void *win = quiet_rows != nullptr && mi == 0 && window <= kWinMaxW && V < (1ll << 30)
+                        ? ks.o2_stream_win[full] : nullptr;
+        const int bpc = o.o2_blocks_per_cu > 0 ? o.o2_blocks_per_cu : win ? 5 : 8;
         const int64_t hcap = hog_max_blocks(o, V, wpb, o.rows_per_wave);
         int64_t blocks = (P + wpb - 1) / wpb;
         if (blocks > (int64_t)num_cus(dev) * bpc) blocks = (int64_t)num_cus(dev) * bpc;
@@ -177,7 +181,9 @@ extern "C" int come_sgns_o2_ex(float *node, float *ctx, int64_t V, int d, const 
         // run, the same speed there: nearly every row is hot and atomic-bound).
         if (o.o2_kernel == 3 || V >= kStreamRowsPerWave * wpb * blocks) {
             if (!o.o2_static) a.counter = launch_counter(dev, stream);  // else grid-stride
-            return launch(o, ks.o2_stream[full][mi], &a, P, mode, wpb, bpc, 0, stream, hcap);
+            if (win) a.quiet = quiet_rows;
+            return launch(o, win ? win : ks.o2_stream[full][mi], &a, P, mode, wpb, bpc, 0, stream,
+                          hcap);
         }
     }
     // LDS ring of the sequential kernel: (2w+1) rows + their ids
@@ -189,6 +195,25 @@ extern "C" int come_sgns_o2_ex(float *node, float *ctx, int64_t V, int d, const 
     return launch(o, ks.o2_direct[full][mi], &a, P, mode, wpb,
                   o.o2_blocks_per_cu > 0 ? o.o2_blocks_per_cu : 6, 0, stream,
                   hog ? hog_max_blocks(o, V, wpb, o.rows_per_wave) : 0);
+}
+
+extern "C" int come_sgns_o2_ex(float *node, float *ctx, int64_t V, int d, const int32_t *walks,
+                               int64_t P, int L, const uint64_t *seeds, int window, int negative,
+                               const uint32_t *table, uint64_t T, float lr, float alpha, int mode,
+                               const uint32_t *hot_rows, const come_launch_opts *opts,
+                               void *stream) {
+    return sgns_o2_impl(node, ctx, V, d, walks, P, L, seeds, window, negative, table, T, lr, alpha,
+                        mode, hot_rows, nullptr, opts, stream);
+}
+
+extern "C" int come_sgns_o2_quiet(float *node, float *ctx, int64_t V, int d, const int32_t *walks,
+                                  int64_t P, int L, const uint64_t *seeds, int window,
+                                  int negative, const uint32_t *table, uint64_t T, float lr,
+                                  float alpha, int mode, const uint32_t *hot_rows,
+                                  const uint32_t *quiet_rows, const come_launch_opts *opts,
+                                  void *stream) {
+    return sgns_o2_impl(node, ctx, V, d, walks, P, L, seeds, window, negative, table, T, lr, alpha,
+                        mode, hot_rows, quiet_rows, opts, stream);
 }
 
 extern "C" int come_sgns_o2(float *node, float *ctx, int64_t V, int d, const int32_t *walks,

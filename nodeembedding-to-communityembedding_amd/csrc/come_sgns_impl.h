@@ -326,6 +326,9 @@ struct O2Args {
     int wb_atomic;   // direct kernel: row updates written as float-atomic deltas (none lost)
     const uint32_t *hot;  // HOG, optional: bitmap of contended rows (come_hot_rows); their
                           // updates are float-atomic deltas, their reads are per pair
+    const uint32_t *quiet;  // windowed stream kernel, optional: bitmap of rows few other wavefronts
+                            // visit (come_quiet_rows); as input rows they stay in the wavefront's
+                            // LDS ring while a position holding them is inside the walk window
 };
 
 // Row r is in the hot bitmap (wave-uniform r: one scalar load).
@@ -866,15 +869,29 @@ __global__ void __launch_bounds__(128) k_sgns_o2_ring(O2Args a) {
 // the spread, so the cap stays as it was).  Wider rows / more negatives keep their natural size:
 // C5's <4, true, 10> held to 4 waves per SIMD ran 3.57 vs 2.10 s per 1M-walk launch
 // (profiles/r05_ab_c5_waves.txt).
-template <int VEC, int MAXN>
+// WINDOW (VEC <= 2, w <= kWinMaxW, V < 2^30): input rows marked quiet (a.quiet) are read once per
+// stay in the walk window and written back once when they leave it.  Each wavefront keeps a ring
+// of 2 kWinMaxW + 1 rows in LDS (5,632 B at d = 128: five 4-wave workgroups per CU, so it is
+// compiled for 5 waves per SIMD); lane s of `ring_ids` names the row slot s holds.  A position's
+// row enters the ring with its first pair (read by the usual prefetch, stored to the slot instead
+// of memory after `in += work`), later prefetches of it are skipped, and the same row at two
+// positions of the window shares one slot.  When the center moves, every slot whose row is at no
+// position of the new window is stored to memory; the rest at the walk's end.  Hot and ordinary
+// rows take the path above unchanged, and one wavefront computes bit for bit what the kernel
+// without the ring does (the ring holds the stored value).
+constexpr int kWinMaxW = 5;
+constexpr int kWinSlots = 2 * kWinMaxW + 1;
+
+template <int VEC, int MAXN, bool WINDOW>
 constexpr int stream_waves_per_eu() {
-    return (VEC <= 2 && MAXN <= 5) ? 8 : 1;
+    return WINDOW ? 5 : (VEC <= 2 && MAXN <= 5) ? 8 : 1;
 }
 
-template <int VEC, bool FULL, int MAXN>
+template <int VEC, bool FULL, int MAXN, bool WINDOW = false>
 __global__ void __launch_bounds__(256)
-    __attribute__((amdgpu_waves_per_eu(stream_waves_per_eu<VEC, MAXN>())))
+    __attribute__((amdgpu_waves_per_eu(stream_waves_per_eu<VEC, MAXN, WINDOW>())))
     k_sgns_o2_stream(O2Args a) {
+    static_assert(!WINDOW || VEC <= 2, "the window ring holds rows of d <= 128");
     using R = Row<VEC, FULL>;
     const int lane = threadIdx.x & 63;
     const int64_t waves_per_block = blockDim.x >> 6;
@@ -892,6 +909,8 @@ __global__ void __launch_bounds__(256)
     // patching the prefetched registers (see the write-back below)
     constexpr bool kReread = VEC <= 2;
     constexpr uint32_t kHotBit = 0x80000000u;
+    constexpr uint32_t kQuietBit = WINDOW ? 0x40000000u : 0u;  // walk positions only
+    constexpr uint32_t kFlagBits = kHotBit | kQuietBit;
     constexpr int kWaitVm0 = 0x0F70;  // s_waitcnt vmcnt(0), no other counter (gfx9 encoding)
     // the exp table in LDS, staged once per workgroup (4,000 bytes): a lookup is one ds_read
     // instead of two dependent scalar-memory loads, and the plain body does all (1 + n) at once
@@ -906,6 +925,13 @@ __global__ void __launch_bounds__(256)
     // and its window of 128 walk positions (encoded rows, see chunk() below), for the same reason
     __shared__ int s_walk[4][128];
     int *wpos = s_walk[threadIdx.x >> 6];
+    // WINDOW: this wavefront's ring of quiet input rows, slot s at [s][i][lane] (element
+    // lane + 64 i, the registers' layout)
+    float *ring = nullptr;
+    if constexpr (WINDOW) {
+        __shared__ float s_ring[4][kWinSlots * 64 * VEC];
+        ring = s_ring[threadIdx.x >> 6];
+    }
 
     for (int64_t p = a.counter ? next_unit(a.counter, 0, 0, lane) : gw; p < a.P;
          p = next_unit(a.counter, p, nwaves, lane)) {
@@ -919,6 +945,9 @@ __global__ void __launch_bounds__(256)
             if (!valid_row(v)) return -1;
             if (a.hot != nullptr && ((a.hot[(uint32_t)v >> 5] >> (v & 31)) & 1u))
                 v = (int)((uint32_t)v | kHotBit);
+            else if (WINDOW && a.quiet != nullptr &&
+                     ((a.quiet[(uint32_t)v >> 5] >> (v & 31)) & 1u))
+                v = (int)((uint32_t)v | kQuietBit);
             return v;
         };
         int wbase = 0;
@@ -937,6 +966,7 @@ __global__ void __launch_bounds__(256)
         };
         // ---- pairs in the reference order (pyx:494-508): center i ascending, j ascending ----
         int it_i = 0, it_j = -1;
+        bool nqj = false;  // WINDOW: the pair next_pair() produced has a quiet input row
         auto next_pair = [&](int &ci, int &cj, int &pi, bool &hi, bool &hj) -> bool {
             for (;;) {
                 if (it_i >= path_len) return false;
@@ -954,8 +984,9 @@ __global__ void __launch_bounds__(256)
                 if (j == i) continue;
                 const int rcj = raw_at(j);
                 if (rcj == -1) continue;  // pyx:504
-                ci = (int)((uint32_t)rci & ~kHotBit);
-                cj = (int)((uint32_t)rcj & ~kHotBit);
+                ci = (int)((uint32_t)rci & ~kFlagBits);
+                cj = (int)((uint32_t)rcj & ~kFlagBits);
+                if constexpr (WINDOW) nqj = ((uint32_t)rcj & kQuietBit) != 0;
                 hi = ((uint32_t)rci & kHotBit) != 0;
                 hj = ((uint32_t)rcj & kHotBit) != 0;
                 pi = i;
@@ -1004,8 +1035,24 @@ __global__ void __launch_bounds__(256)
         auto next_target = [&](int k) {
             return k <= n ? (int)(readlane_u32(ids, 32 + k) & ~kHotBit) : -1;
         };
+        // WINDOW: the row each ring slot holds, slot s in lane s (-1 = free)
+        int ring_ids = -1;
+        auto ring_find = [&](int id) {  // the slot holding row id, or -1
+            const uint64_t m = __ballot(ring_ids == id);
+            return m ? (int)__builtin_ctzll(m) : -1;
+        };
+        auto ring_write_back = [&](int s) {  // slot s -> memory, and free
+            const int id = (int)readlane_u32((uint32_t)ring_ids, s);
+            R out;
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) out.v[e] = ring[(s * VEC + e) * 64 + lane];
+            out.store(a.node + (int64_t)id * d, lane, d);
+            ring_ids = lane == s ? -1 : ring_ids;
+        };
         auto prefetch = [&](bool need_pos) {
-            in_n.load(a.node + (int64_t)ncj * d, lane, d);
+            bool held = false;  // a quiet row already in the ring is not read again
+            if constexpr (WINDOW) held = nqj && ring_find(ncj) >= 0;
+            if (!held) in_n.load(a.node + (int64_t)ncj * d, lane, d);
             if (need_pos) pos_n.load(a.ctx + (int64_t)nci * d, lane, d);
             // lane 32 + k <- draw used + k - 1 (k <= n; used + n <= 127)
             const bool drawn = lane > 32 && lane <= 32 + n;
@@ -1039,6 +1086,7 @@ __global__ void __launch_bounds__(256)
             // ---- the next pair becomes the current one ----
             const int ci = nci, cj = ncj, ic = npi;
             const bool hot_ci = nhi, hot_cj = nhj;
+            const bool quiet_cj = WINDOW && nqj;
             R in = in_n;
             int t[MAXN + 1];
             R r[MAXN + 1];
@@ -1056,6 +1104,34 @@ __global__ void __launch_bounds__(256)
             }
             if (new_center) pos_upd = false;
             prev_i = ic;
+            int slot = -1;  // WINDOW: the ring slot of this pair's input row
+            if constexpr (WINDOW) {
+                uint64_t occ = new_center ? __ballot(ring_ids >= 0) : 0;
+                if (occ) {
+                    // rows at the new window's positions, one per lane; a slot whose row is at
+                    // none of them has left the window
+                    // slide the index window up to the last of them first
+                    (void)raw_at(ic + w < path_len ? ic + w : path_len - 1);
+                    const int q = ic - w + lane;
+                    int wid = -1;
+                    if (lane <= 2 * w && q >= 0 && q < path_len) {
+                        const int v = wpos[q - wbase];
+                        wid = v == -1 ? -1 : (int)((uint32_t)v & ~kFlagBits);
+                    }
+                    while (occ) {
+                        const int s = __builtin_ctzll(occ);
+                        occ &= occ - 1;
+                        const int id = (int)readlane_u32((uint32_t)ring_ids, s);
+                        if (__ballot(wid == id) == 0) ring_write_back(s);
+                    }
+                }
+                if (quiet_cj) {
+                    slot = ring_find(cj);
+                    if (slot >= 0)
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) in.v[e] = ring[(slot * VEC + e) * 64 + lane];
+                }
+            }
             // the next pair's ids move to lanes [0, 32) (v_permlane32_swap: {lower, upper} halves
             // broadcast); prefetch() then writes the pair after it into lanes [32, 32 + MAXN]
             ids = (uint32_t)__builtin_amdgcn_permlane32_swap((int)ids, (int)ids, false, false)[1];
@@ -1255,7 +1331,22 @@ __global__ void __launch_bounds__(256)
             } else {
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) in.v[e] = in.v[e] + work.v[e];
-                in.store(a.node + (int64_t)cj * d, lane, d);
+                bool to_ring = false;
+                if constexpr (WINDOW) {
+                    if (quiet_cj && slot < 0) {  // first pair of its stay: take a free slot
+                        const uint64_t free_slots =
+                            ~__ballot(ring_ids >= 0) & ((1ull << kWinSlots) - 1ull);
+                        if (free_slots) {  // always: at most 2w rows of the window are held
+                            slot = __builtin_ctzll(free_slots);
+                            ring_ids = lane == slot ? cj : ring_ids;
+                        }
+                    }
+                    to_ring = quiet_cj && slot >= 0;
+                    if (to_ring)
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) ring[(slot * VEC + e) * 64 + lane] = in.v[e];
+                }
+                if (!to_ring) in.store(a.node + (int64_t)cj * d, lane, d);
             }
             if (kReread) {
                 if (!plain && have) {
@@ -1271,6 +1362,14 @@ __global__ void __launch_bounds__(256)
             } else if (have && ncj == cj) {
 #pragma unroll
                 for (int e = 0; e < VEC; ++e) in_n.v[e] += work.v[e];
+            }
+        }
+        if constexpr (WINDOW) {  // rows still in the ring at the walk's end
+            uint64_t occ = __ballot(ring_ids >= 0);
+            while (occ) {
+                const int s = __builtin_ctzll(occ);
+                occ &= occ - 1;
+                ring_write_back(s);
             }
         }
         if (a.upd_count && lane == 0 && nupd) atomicAdd(a.upd_count, (unsigned long long)nupd);
@@ -1570,6 +1669,7 @@ struct KernelSet {
     void *o2_direct[2][3];  // [FULL][maxn idx]
     void *o2_ring[2][3];    // sequential mode
     void *o2_stream[2][3];  // Hogwild mode
+    void *o2_stream_win[2];  // Hogwild mode with quiet rows: VEC <= 2, n <= 5 (else nullptr)
     void *o1[2][3];
     void *o1_runs[2][3];
 };

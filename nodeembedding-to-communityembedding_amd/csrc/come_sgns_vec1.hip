@@ -21,6 +21,7 @@ const KernelSet &kernels_vec1() {
         k.o1_runs[0][2] = (void *)&k_sgns_o1_runs<1, false, 20>;
         k.o2_ring[0][2] = (void *)&k_sgns_o2_ring<1, false, 20>;
         k.o2_stream[0][2] = (void *)&k_sgns_o2_stream<1, false, 20>;
+        k.o2_stream_win[0] = (void *)&k_sgns_o2_stream<1, false, 5, true>;
         return k;
     }();
     return ks;

@@ -36,6 +36,8 @@ const KernelSet &kernels_vec2() {
         k.o1_runs[1][2] = (void *)&k_sgns_o1_runs<2, true, 20>;
         k.o2_ring[1][2] = (void *)&k_sgns_o2_ring<2, true, 20>;
         k.o2_stream[1][2] = (void *)&k_sgns_o2_stream<2, true, 20>;
+        k.o2_stream_win[0] = (void *)&k_sgns_o2_stream<2, false, 5, true>;
+        k.o2_stream_win[1] = (void *)&k_sgns_o2_stream<2, true, 5, true>;
         return k;
     }();
     return ks;

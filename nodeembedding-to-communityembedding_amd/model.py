@@ -167,6 +167,28 @@ class Model(object):
                                       max(1, int(share * self.table.numel())))
         return cache[key]
 
+    def quiet_rows(self, waves, window, eps=None, hot_share=None):
+        """Bitmap (CUDA) of the quiet node-table rows for a Hogwild launch with `waves` wavefronts
+        in flight and this window: rows that are not hot (hot_rows(hot_share)) and whose expected
+        number of concurrent visitors, waves x (2 window + 1) x the row's share of walk visits, is
+        at most eps (default training_sdg_inner.DEFAULT_QUIET_EPS) -- come_quiet_rows.  The share
+        is recovered from the table, which holds row v's count in the slots of node id v + 1: only
+        a vocabulary of ids 1..V has quiet rows.  None where there are none (tables not on a GPU,
+        eps <= 0, other ids).  Cached like hot_rows."""
+        from . import training_sdg_inner as tsi
+        eps = tsi.DEFAULT_QUIET_EPS if eps is None else float(eps)
+        share = tsi.default_hot_share(self.layer1_size) if hot_share is None else float(hot_share)
+        if not getattr(self.table, "is_cuda", False) or eps <= 0 or not self._contiguous:
+            return None
+        T = int(self.table.numel())
+        visitors = float(waves) * (2 * int(window) + 1)
+        hot_min = max(1, int(share * T)) if share > 0 else T + 1
+        cache = self.__dict__.setdefault("_hot_cache", {})
+        key = ("quiet", eps, visitors, hot_min, self.table.data_ptr(), int(self.vocab_size), T)
+        if key not in cache:
+            cache[key] = tsi.quiet_rows(self.table, self.vocab_size, visitors, eps, hot_min)
+        return cache[key]
+
     def negative_table(self):
         """What the trainers pass to the kernels: the exact packed form of the uint32 table
         (come_pack_table: same draws, 16 B per 64 slots -- 25 MB instead of 400 MB at T = 1e8),

@@ -160,6 +160,34 @@ def hot_rows(table, V, min_count):
     return bits
 
 
+def quiet_rows(table, V, visitors, eps, hot_min_count, power=0.75, id_shift=1):
+    """Bitmap (CUDA int32 tensor [ceil(V/32)]) of the quiet rows of the node table, from the plain
+    negative table `table` (CUDA uint32-as-int32 [T]): come_quiet_rows (include/come.h) -- rows
+    that are not hot and whose expected number of concurrent visitors, visitors x the row's share
+    of walk visits, is at most eps."""
+    import torch
+    _require_cuda(table, "table", torch.int32)
+    counts = torch.empty(int(V), dtype=torch.int32, device=table.device)
+    total = torch.empty(1, dtype=torch.float64, device=table.device)
+    bits = torch.empty((int(V) + 31) // 32, dtype=torch.int32, device=table.device)
+    check(_lib.lib().come_quiet_rows(ptr(table), table.numel(), int(V), float(power),
+                                     int(id_shift), float(visitors), float(eps),
+                                     int(hot_min_count), ptr(counts), ptr(total), ptr(bits),
+                                     stream_handle(table.device)), "come_quiet_rows")
+    return bits
+
+
+# Rows with at most this many expected concurrent visitors (wavefronts in flight x (2w + 1) x the
+# row's share of walk visits) are "quiet": the windowed stream kernel keeps them on chip over a
+# walk window (DESIGN.md §3.1).  The largest of the swept values (0.05 / 0.1 / 0.2 / 0.4) whose
+# held-out loss stays within half of the parent's distance to the 1% bar, at the bench's launch and
+# at 100k nodes: all four did, and the loss moved towards the sequential oracle's
+# (profiles/r13_ab_input_window.txt).
+DEFAULT_QUIET_EPS = 0.4
+# four-wave workgroups per CU of a launch with quiet rows (come_sgns_o2_quiet's default grid)
+QUIET_BLOCKS_PER_CU = 5
+
+
 def _hot_arg(hot, node, V):
     """(pointer, mode flag) for the contended-row argument: "auto" -> NULL (libcome derives the
     bitmap from the table at default_hot_share(d)), None -> COME_HOT_NONE (every row cold), else a CUDA
@@ -182,7 +210,7 @@ def _hot_arg(hot, node, V):
 
 
 def sgns_o2(node, ctx, walks, seeds, window, negative, table, lr, alpha=1.0, mode=MODE_HOGWILD,
-            opts=None, update_count=None, hot="auto"):
+            opts=None, update_count=None, hot="auto", quiet=None):
     """Batched train_o2: every walk of ``walks`` [P, L] (int32 rows, -1 = None) in one launch.
 
     node, ctx: float32 CUDA tensors [V, d], updated in place.  seeds: uint64 (stored as int64)
@@ -195,7 +223,9 @@ def sgns_o2(node, ctx, walks, seeds, window, negative, table, lr, alpha=1.0, mod
     with float atomics), "auto" (default: derived from `table` by the library at default_hot_share(d)
     before EVERY launch, ~0.1 ms at T = 1e8 -- callers launching many small batches pass
     Model.hot_rows() instead, as the trainers do) or None (no contended rows: every row updated
-    with plain stores)."""
+    with plain stores); quiet: the quiet-row bitmap of quiet_rows() or None (default: none) --
+    Hogwild launches of the streaming kernel at d <= 128, negative <= 5, window <= 5 keep those
+    input rows in LDS over a walk window (come_sgns_o2_quiet); every other launch ignores it."""
     import torch
     _require_cuda(node, "node", torch.float32)
     _require_cuda(ctx, "ctx", torch.float32)
@@ -210,11 +240,14 @@ def sgns_o2(node, ctx, walks, seeds, window, negative, table, lr, alpha=1.0, mod
         walks = walks[:, :MAX_SENTENCE_LEN].contiguous()
     V, d = node.shape
     hp, hflag = _hot_arg(hot, node, V)
-    rc = _lib.lib().come_sgns_o2_ex(ptr(node), ptr(ctx), V, d, ptr(walks), walks.shape[0],
-                                    walks.shape[1], ptr(seeds), int(window), int(negative),
-                                    tp, T, float(lr), float(alpha), int(mode) | flag | hflag,
-                                    hp, _opts_arg(opts, update_count),
-                                    stream_handle(node.device))
+    qp = None
+    if quiet is not None:
+        qp, _ = _hot_arg(quiet, node, V)
+    rc = _lib.lib().come_sgns_o2_quiet(ptr(node), ptr(ctx), V, d, ptr(walks), walks.shape[0],
+                                       walks.shape[1], ptr(seeds), int(window), int(negative),
+                                       tp, T, float(lr), float(alpha), int(mode) | flag | hflag,
+                                       hp, qp, _opts_arg(opts, update_count),
+                                       stream_handle(node.device))
     check(rc, "come_sgns_o2")
 
 
