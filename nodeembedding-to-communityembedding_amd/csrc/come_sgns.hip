@@ -111,6 +111,21 @@ static int check_common(int64_t V, int d, int negative, const uint32_t *table, u
     return COME_OK;
 }
 
+// The hot bitmap of a launch: none on request (COME_HOT_NONE); a Hogwild launch given none derives
+// it from the negative table.
+static int resolve_hot_rows(int mode, int hot_none, const uint32_t *table, uint64_t T, int packed,
+                            int64_t V, int d, void *stream, const uint32_t **hot_rows) {
+    if (hot_none) {
+        *hot_rows = nullptr;
+    } else if (mode == COME_MODE_HOGWILD && *hot_rows == nullptr && table != nullptr && T > 0) {
+        int dev = 0;
+        const int rc = ensure_init(&dev);
+        if (rc) return rc;
+        return derive_hot_rows(dev, table, T, packed, V, d, stream, hot_rows);
+    }
+    return COME_OK;
+}
+
 static bool aligned_for(const void *p, int d) {
     const int vec = (d + 63) / 64;
     if (d != 64 * vec || vec < 2) return true;
@@ -136,15 +151,8 @@ static int sgns_o2_impl(float *node, float *ctx, int64_t V, int d, const int32_t
         return set_error(COME_E_INVALID, "null node/ctx/walks/seeds pointer");
     if (!aligned_for(node, d) || !aligned_for(ctx, d))
         return set_error(COME_E_INVALID, "node/ctx must be 16-byte aligned for d=%d", d);
-    if (hot_none) {
-        hot_rows = nullptr;
-    } else if (mode == COME_MODE_HOGWILD && hot_rows == nullptr && table != nullptr && T > 0) {
-        int dev = 0;
-        rc = ensure_init(&dev);
-        if (rc) return rc;
-        rc = derive_hot_rows(dev, table, T, packed, V, d, stream, &hot_rows);
-        if (rc) return rc;
-    }
+    rc = resolve_hot_rows(mode, hot_none, table, T, packed, V, d, stream, &hot_rows);
+    if (rc) return rc;
     O2Args a{node, ctx, walks, seeds, table, V, P, L, d, window, negative, lr, alpha,
              make_fastmod(T), packed, nullptr,
              reinterpret_cast<unsigned long long *>(o.o2_update_count), o.o2_fresh_loads,
@@ -239,15 +247,8 @@ extern "C" int come_sgns_o1_ex(float *node, int64_t V, int d, const int32_t *edg
         return set_error(COME_E_INVALID, "O1 supports negative <= 32 (got %d)", negative);
     if (!aligned_for(node, d))
         return set_error(COME_E_INVALID, "node must be 16-byte aligned for d=%d", d);
-    if (hot_none) {
-        hot_rows = nullptr;
-    } else if (mode == COME_MODE_HOGWILD && hot_rows == nullptr && table != nullptr && T > 0) {
-        int dev = 0;
-        rc = ensure_init(&dev);
-        if (rc) return rc;
-        rc = derive_hot_rows(dev, table, T, packed, V, d, stream, &hot_rows);
-        if (rc) return rc;
-    }
+    rc = resolve_hot_rows(mode, hot_none, table, T, packed, V, d, stream, &hot_rows);
+    if (rc) return rc;
     // default grid: 8 four-wave workgroups per CU where the run kernel is compiled for 8 waves per
     // SIMD (d <= 128, n <= 5: o1_runs_waves_per_eu), else 6
     const int bpc = o.o1_blocks_per_cu > 0 ? o.o1_blocks_per_cu
@@ -270,9 +271,7 @@ extern "C" int come_sgns_o1_ex(float *node, int64_t V, int d, const int32_t *edg
     if (chunk > 0)  // one wavefront per chunk of consecutive edges, the input row held
         return launch(o, ks.o1_runs[full][maxn_index(negative)], &a, (E + chunk - 1) / chunk, mode,
                       4, bpc, 0, stream, hcap);
-    return launch(o, ks.o1[full][maxn_index(negative)], &a, E, mode, 4,
-                  o.o1_blocks_per_cu > 0 ? o.o1_blocks_per_cu : 6, 0, stream,
-                  mode == COME_MODE_HOGWILD ? hog_max_blocks(o, V, 4, o.o1_rows_per_wave) : 0);
+    return launch(o, ks.o1[full][maxn_index(negative)], &a, E, mode, 4, bpc, 0, stream, hcap);
 }
 
 extern "C" int come_sgns_o1(float *node, int64_t V, int d, const int32_t *edges, int64_t E,

@@ -6,7 +6,7 @@
 // rows t_1..t_n:
 //   pair = softplus(-f(a, b)) + sum_k softplus(f(a, t_k)),   softplus(z) = log(1 + e^z)
 // the exact objective (no +-6 skip, no sigmoid table).  f is the trainer's fp32 dot (lane_partial
-// + the xor butterfly of come_sgns_impl.h), softplus is float64 on that fp32 value.
+// + the xor butterfly of come_sgns_common.h), softplus is float64 on that fp32 value.
 //   k_sgns_o2_loss     one wavefront per walk: the centre's ctx row stays in registers over its
 //                      window partners, the window's walk entries sit one per lane (spans of at
 //                      most 64 positions), negatives come from the trainer's DrawBatch
@@ -21,7 +21,7 @@
 #include <math.h>
 
 #include "come_c4.h"
-#include "come_sgns_impl.h"
+#include "come_sgns_common.h"
 
 namespace come {
 

@@ -6,7 +6,7 @@
 // Every kernel touches a 2 GiB table (8x the 256 MiB Infinity Cache), each row / line exactly
 // once per launch in a scattered order (a multiplicative bijection), so no access is served from
 // L2 or the Infinity Cache.  Rows are 512 B (d = 128 fp32) and are accessed
-// exactly as Row<2, true> does in come_sgns_impl.h: lane l moves elements l and l + 64, i.e. two
+// exactly as Row<2, true> does in come_sgns_common.h: lane l moves elements l and l + 64, i.e. two
 // dword-per-lane wave instructions of 256 contiguous bytes each.
 //   k_row_read     random rows read (known read bytes = rows * 512)
 //   k_row_rmw      random rows read + written with plain stores (read = write = rows * 512)

@@ -100,6 +100,25 @@ def test_o2_kat_bit_exact_vs_oracle_and_golden(name):
     (128, 20, 1, 3, 10, 3, 100),         # V = 3: nearly every draw repeats
 ])
 def test_o2_random_bit_exact_vs_oracle(d, neg, w, V, L, P, T):
+    check_o2_random_vs_oracle(d, neg, w, V, L, P, T)
+
+
+@pytest.mark.parametrize("d,neg,w,V,L,P,T", [
+    (64, 5, 3, 100, 25, 10, 4000),
+    (96, 7, 4, 100, 25, 6, 4000),        # masked layout, MAXN = 10
+    (128, 10, 5, 40, 30, 8, 3000),       # small V: many repeated negatives / positive hits
+    (256, 10, 5, 500, 40, 6, 20000),
+    (33, 15, 6, 80, 30, 5, 3000),        # MAXN = 20
+    (128, 20, 1, 3, 10, 3, 100),         # V = 3: nearly every draw repeats
+])
+def test_o2_direct_kernel_bit_exact_vs_oracle(d, neg, w, V, L, P, T):
+    """The direct kernel (o2_kernel=1) on shapes the sequential mode gives to the ring kernel:
+    both layouts, the three MAXN buckets, and vocabularies small enough that nearly every pair
+    repeats a negative or draws its positive."""
+    check_o2_random_vs_oracle(d, neg, w, V, L, P, T, opts={"o2_kernel": 1})
+
+
+def check_o2_random_vs_oracle(d, neg, w, V, L, P, T, opts=None):
     rng = np.random.RandomState(d * 1000 + neg * 10 + V)
     counts = rng.randint(1, 100, V)
     table = orc.make_table(counts, T)
@@ -108,7 +127,7 @@ def test_o2_random_bit_exact_vs_oracle(d, neg, w, V, L, P, T):
     walks = rng.randint(0, V, (P, L)).astype(np.int32)
     walks[rng.uniform(size=walks.shape) < 0.05] = -1
     seeds = rng.randint(0, 2 ** 48, P, dtype=np.int64).astype(np.uint64)
-    node, ctx = run_o2(node0, ctx0, walks, seeds, w, neg, table, 0.05, 0.9)
+    node, ctx = run_o2(node0, ctx0, walks, seeds, w, neg, table, 0.05, 0.9, opts=opts)
     n_ref, c_ref = node0.copy(), ctx0.copy()
     orc.sgns_o2(n_ref, c_ref, walks, seeds, w, neg, table, 0.05, 0.9, dot_mode=orc.DOT_WAVE64)
     np.testing.assert_array_equal(node, n_ref)
