@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* ABI 5, additive: come_gmm_estep_diag, come_gmm_diag_scratch, come_gmm_diag_moments,
+/* ABI 5, additive: come_random_walks_pq and its CPU twin come_cpu_random_walks_pq (node2vec
+ * (p, q) second-order walks; come_random_walks is unchanged).
+ * ABI 5, additive: come_gmm_estep_diag, come_gmm_diag_scratch, come_gmm_diag_moments,
  * come_gmm_diag_scatter, come_community_grad_diag and come_community_loss_diag (diagonal
  * covariances: the GMM EM, the community step and the community loss for covariance_type='diag').
  * ABI 5, additive: come_sgns_o2_loss, come_sgns_pairs_loss and their CPU twins (the SGNS
@@ -405,6 +407,27 @@ int come_random_walks(const int64_t *rowptr, const int32_t *col, int64_t V,
                       uint64_t seed, int64_t walk_offset, const int32_t *emit, int32_t *out,
                       void *stream);
 
+/* Device walker with node2vec's return / in-out bias (p, q): a second-order walk.  The first
+ * step of a walk, and the first after a restart, is come_random_walks' step (same Philox block,
+ * same draws); every later step goes from cur (previous node prev) to x in N(cur) with
+ * probability proportional to 1/p if x == prev, 1 if x is in N(prev), 1/q otherwise.  Dead ends,
+ * restarts (after which the walk has no prev), starts, emit, out, seed and walk_offset as
+ * come_random_walks; p = q = 1 gives come_random_walks' walks bit for bit.  A walk depends only
+ * on (seed, walk_offset + walk, start, graph, alpha, p, q).  Exact rejection sampling, O(1)
+ * expected trials per step (at most 2 max(q, 1/q)), capped: csrc/come_walk_pq.h.
+ *   p in [2^-8, 2^8], q in [2^-4, 2^4]; anything else (NaN too) is COME_E_INVALID.
+ *   col_sorted: device int32, the rowptr of col with each row ascending (membership searches;
+ *     candidates are always drawn from col, so every step is an entry of col's row whatever
+ *     col_sorted's order).  May equal col when col's rows are ascending; may be NULL iff q == 1
+ *     and p >= 1 (no search runs then).
+ *   trials_out: NULL, or one device uint64 to which the launch adds the Philox blocks it drew:
+ *     one per step taken plus one per rejected trial (nothing at a dead end).
+ * P == 0 or path_length == 0 is a no-op; a validation failure writes nothing.  Asynchronous. */
+int come_random_walks_pq(const int64_t *rowptr, const int32_t *col, const int32_t *col_sorted,
+                         int64_t V, const int32_t *starts, int64_t P, int path_length,
+                         float alpha, float p, float q, uint64_t seed, int64_t walk_offset,
+                         const int32_t *emit, int32_t *out, uint64_t *trials_out, void *stream);
+
 /* Host, exact: build_deepwalk_corpus_iter (graph_utils.py:187-192) with the reference's own
  * random stream.  n_streams independent CPython random.Random streams (one per walk file of
  * write_walks_to_disk :122-146); stream s writes paths_per_stream[s] passes of V walks, streams
@@ -671,6 +694,14 @@ int come_cpu_sgns_pairs_loss(const float *inp, const float *out, int64_t V, int 
                              const int32_t *rows_in, const int32_t *rows_pos,
                              const int32_t *rows_neg, int64_t M, int negative, double *pair_out,
                              double *loss_out, int64_t *pairs_out, int threads);
+/* come_random_walks_pq on host pointers (trials_out: one host uint64, added to, or NULL): the
+ * kernel's own step body (csrc/come_walk_pq.h), so the walks and the trial count are the
+ * device's bit for bit, whatever `threads`. */
+int come_cpu_random_walks_pq(const int64_t *rowptr, const int32_t *col, const int32_t *col_sorted,
+                             int64_t V, const int32_t *starts, int64_t P, int path_length,
+                             float alpha, float p, float q, uint64_t seed, int64_t walk_offset,
+                             const int32_t *emit, int32_t *out, uint64_t *trials_out,
+                             int threads);
 
 /* ---- Host helpers ---- */
 

@@ -77,7 +77,9 @@ class Context2Vec(object):
         self.hot_share = hot_share      # None = training_sdg_inner.default_hot_share(d)
         self.launch_opts = launch_opts  # per-call come_launch_opts fields (A/B runs)
         # rows with at most this many expected concurrent visitors stay on chip over a walk window
-        # (Model.quiet_rows; None = training_sdg_inner.DEFAULT_QUIET_EPS, 0 = off)
+        # (Model.quiet_rows; None = training_sdg_inner.DEFAULT_QUIET_EPS, 0 = off).  The rule takes
+        # a row's share of walk visits from its degree share, which walks with a node2vec bias
+        # (graph.random_walks(p=, q=)) do not follow: a rougher estimate for them.
         self.quiet_eps = quiet_eps
         self.combine = combine          # DeltaAllReduce combine rule
         self._exchanges = {}

@@ -10,6 +10,7 @@ to them.
     community_loss(x, pi, prec_chol, mu_prec, log_norm, threads) -> total   (what :40-59 means)
     sgns_o2_loss(node, ctx, walks, seeds, window, negative, table) -> (total, pairs[, per walk])
     sgns_pairs_loss(inp, out, rows_in, rows_pos, rows_neg)         -> (total, counted[, per pair])
+    random_walks_pq(rowptr, col, starts, path_length, alpha, p, q, seed, ...) -> walks[, trials]
 
 Tables are updated in place (float32, C-contiguous, as the reference's numpy arrays).  ``mode``:
 MODE_HOGWILD = ``threads`` workers taking jobs of 150 walks / edges with lock-free updates, as the
@@ -186,3 +187,48 @@ def sgns_pairs_loss(inp, out, rows_in, rows_pos, rows_neg=None, return_pairs=Fal
           "come_cpu_sgns_pairs_loss")
     return (total.value, counted.value, per_pair) if return_pairs else (total.value,
                                                                          counted.value)
+
+
+def sorted_adjacency(rowptr, col):
+    """``col`` with each row ascending (numpy form of graph_utils.sorted_adjacency): one sort of
+    the (row << 32) | col keys."""
+    _arr(rowptr, np.int64, "rowptr")
+    _arr(col, np.int32, "col")
+    row = np.repeat(np.arange(len(rowptr) - 1, dtype=np.int64), np.diff(rowptr))
+    key = np.sort((row << 32) | col.astype(np.int64))
+    return (key & 0xFFFFFFFF).astype(np.int32)
+
+
+def random_walks_pq(rowptr, col, starts, path_length, alpha=0.0, p=1.0, q=1.0, seed=0,
+                    walk_offset=0, emit=None, col_sorted=None, out=None, return_trials=False,
+                    threads=None):
+    """come_cpu_random_walks_pq: node2vec (p, q) second-order walks, the device walker's
+    (graph_utils.device_walks(..., p, q)) bit for bit.  rowptr int64 [V+1], col int32 (positions,
+    non-negative), starts int32 [P]; ``col_sorted`` (each row of col ascending) is built when it is
+    needed and not given.  Returns int32 [P, path_length] (-1 after a walk ends), or
+    ``(walks, trials)`` with ``return_trials``: the Philox blocks drawn, one per step taken plus
+    one per rejected trial; it does not depend on ``threads``."""
+    _arr(rowptr, np.int64, "rowptr")
+    _arr(col, np.int32, "col")
+    _arr(starts, np.int32, "starts")
+    V, P = len(rowptr) - 1, len(starts)
+    if emit is not None:
+        _arr(emit, np.int32, "emit")
+        assert emit.shape == (V,)
+    if col_sorted is None and not (float(q) == 1.0 and float(p) >= 1.0):
+        col_sorted = sorted_adjacency(rowptr, col)
+    if col_sorted is not None:
+        _arr(col_sorted, np.int32, "col_sorted")
+        assert col_sorted.shape == col.shape
+    if out is None:
+        out = np.empty((P, int(path_length)), np.int32)
+    else:
+        _arr(out, np.int32, "out", True)
+        assert out.shape == (P, int(path_length))
+    trials = ctypes.c_uint64(0)
+    check(_lib.lib().come_cpu_random_walks_pq(
+        ptr(rowptr), ptr(col), None if col_sorted is None else ptr(col_sorted), V, ptr(starts), P,
+        int(path_length), float(alpha), float(p), float(q), int(seed) & (2 ** 64 - 1),
+        int(walk_offset), None if emit is None else ptr(emit), ptr(out), ctypes.byref(trials),
+        _threads(threads)), "come_cpu_random_walks_pq")
+    return (out, trials.value) if return_trials else out

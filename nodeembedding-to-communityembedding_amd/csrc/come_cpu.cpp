@@ -24,6 +24,9 @@
 //                            come_sgns_pairs_loss define them: the trainer's fp32 WAVE64 dot, a
 //                            float64 softplus on it, terms added in k order, pairs in the
 //                            trainer's order; one partial sum per thread's block of walks (pairs).
+//   come_cpu_random_walks_pq the node2vec (p, q) walker: come_walk_pq.h's step body, which the
+//                            kernel k_random_walks_pq compiles too, so the walks are the device's
+//                            bit for bit; walks split over the threads.
 // Each compute body is built twice, for AVX2+FMA and for the baseline ISA (explicit fmaf either
 // way, -ffp-contract=off: identical results), and the first call picks one from the CPU.
 #include <stdint.h>
@@ -38,6 +41,7 @@
 #include <vector>
 
 #include "../../include/come.h"
+#include "come_walk_pq.h"
 
 namespace come {
 int set_error(int code, const char *fmt, ...);
@@ -661,5 +665,55 @@ extern "C" int come_cpu_sgns_pairs_loss(const float *inp, const float *out, int6
     const SgnsLoss a{inp,     out,     V, d,       negative, 0,        0,       nullptr,
                      nullptr, nullptr, 0, rows_in, rows_pos, rows_neg, pair_out};
     loss_drive(a, M, threads, loss_out, pairs_out);
+    return COME_OK;
+}
+
+// The (p, q) walker on host memory: come_walk_pq.h's pq_step, the kernel's own step body, walk by
+// walk.  A walk depends only on its global index, so the split over threads changes nothing.
+extern "C" int come_cpu_random_walks_pq(const int64_t *rowptr, const int32_t *col,
+                                        const int32_t *col_sorted, int64_t V,
+                                        const int32_t *starts, int64_t P, int L, float alpha,
+                                        float p, float q, uint64_t seed, int64_t walk_offset,
+                                        const int32_t *emit, int32_t *out, uint64_t *trials_out,
+                                        int threads) {
+    using namespace come;
+    if (V <= 0 || V > INT32_MAX)
+        return set_error(COME_E_INVALID, "cpu_random_walks_pq: V must be in [1, 2^31)");
+    if (P < 0 || L < 0 || walk_offset < 0)
+        return set_error(COME_E_INVALID,
+                         "cpu_random_walks_pq: P, L and walk_offset must be >= 0");
+    if (!(alpha >= 0.0f && alpha <= 1.0f))
+        return set_error(COME_E_INVALID, "cpu_random_walks_pq: alpha not in [0,1]");
+    if (!pq_in_range(p, q))
+        return set_error(COME_E_INVALID,
+                         "cpu_random_walks_pq: p must be in [2^-8, 2^8] and q in [2^-4, 2^4]");
+    int rc = check_threads(threads);
+    if (rc) return rc;
+    if (P == 0 || L == 0) return COME_OK;
+    if (!rowptr || !col || !starts || !out)
+        return set_error(COME_E_INVALID, "cpu_random_walks_pq: null pointer");
+    if (!col_sorted && pq_needs_sorted(p, q))
+        return set_error(COME_E_INVALID,
+                         "cpu_random_walks_pq: col_sorted may be NULL only with q == 1 and p >= 1");
+    const PqGraph g{rowptr, col, col_sorted, rowptr[V]};
+    const PqParams pp = pq_make_params(alpha, p, q);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    std::atomic<uint64_t> total(0);
+    parallel_rows(P, threads, [&](int64_t lo, int64_t hi) {
+        uint64_t trials = 0;
+        for (int64_t w = lo; w < hi; ++w) {
+            int32_t *row = out + w * (int64_t)L;
+            const int32_t start = starts[w];
+            const uint64_t gw = (uint64_t)(walk_offset + w);
+            bool alive = start >= 0 && start < V;  // not a node: an empty walk
+            PqWalk s{alive ? start : -1, -1, 0, 0};
+            for (int t = 0; t < L; ++t) {
+                if (alive && t > 0) trials += pq_step(g, pp, start, (uint32_t)t, gw, k0, k1, s, alive);
+                row[t] = alive ? (emit ? emit[s.cur] : s.cur) : -1;
+            }
+        }
+        total += trials;
+    });
+    if (trials_out) *trials_out += total.load();
     return COME_OK;
 }

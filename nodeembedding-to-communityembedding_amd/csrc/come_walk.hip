@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "come_internal.h"
+#include "come_walk_pq.h"  // Philox / philox4x32_10, shared with the (p, q) walker and the CPU twin
 
 namespace come {
 
@@ -31,27 +32,6 @@ struct WalkArgs {
     int L;
     uint32_t restart_threshold;  // restart iff 24-bit uniform < threshold (alpha * 2^24)
 };
-
-struct Philox {
-    uint32_t r[4];
-};
-
-__device__ inline Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
-                                       uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint32_t lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
-        const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0;
-        c1 = lo1;
-        c2 = n2;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return {{c0, c1, c2, c3}};
-}
 
 __global__ void __launch_bounds__(256) k_random_walks(WalkArgs a) {
     const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,0 +1,232 @@
+// come_walk_pq.h -- the walkers' random stream (Philox-4x32-10) and the node2vec (p, q)
+// second-order step: one copy, compiled as device code by come_walk.hip / come_walk_pq.hip and as
+// plain host C++ by come_cpu.cpp (the CPU twin), so the two are the same walks bit for bit.
+//
+// Semantics.  A walk is c_0 = start.  Its first step, and the first step after a restart, is
+// uniform over N(c_0): the first-order walker's step (come_walk.hip), same Philox block, same
+// draws.  Every later step goes from cur = c_{t-1} with prev = c_{t-2} to x in N(cur) with
+// probability proportional to
+//     wr = 1/p   if x == prev,
+//     wa = 1     if x is in N(prev),
+//     wf = 1/q   otherwise.
+// A node without neighbours ends the walk.  With probability alpha a step is instead a jump to
+// `start`, after which the walk has no prev.
+//
+// Sampling: rejection against the envelope M = max(wa, wf), which p does not enter, with the part
+// of the return weight above the envelope handled as an "outlier" (Knuth-Yao style mixture), so a
+// step never costs O(degree) and a large 1/p never makes the other neighbours' acceptance small.
+// Fixed point, units of 2^-32, computed once per call on the host in double (pq_make_params):
+//     ta = wa / M,  tf = wf / M,  tr = min(wr, M) / M     each rounded, clamped to [1, 2^32] and
+//                                                         stored minus one (a uint32)
+//     e  = max(wr - M, 0) / M                             an integer < 2^45 (here <= 255 * 2^32)
+// Step t of global walk gw (= walk_offset + w) runs trials j = 0, 1, ...; trial j draws one Philox
+// block r[0..3] with counter (t, gw low, gw high, j) and the call's key (seed low, seed high):
+//     j == 0 only: restart iff (r[1] >> 8) < ceil(alpha * 2^24)          (the first-order test)
+//     no prev, or deg(cur) == 1: take col[b + ((r[0] * deg) >> 32)]      (the first-order pick);
+//         for deg == 1 that is the only neighbour -- exact, and a leaf never spins for large p
+//     otherwise
+//       1. if e > 0 and prev is in N(cur): return to prev iff r[3] * (deg * 2^32 + e) < e * 2^32,
+//          compared exactly in 128 bits, i.e. with probability e / (deg * 2^32 + e) to within the
+//          2^-32 grain of r[3];
+//       2. else the candidate x = col[b + ((r[0] * deg) >> 32)] is taken iff r[2] <= t(x) - 1,
+//          t(x) = tr, ta or tf by the three cases above;
+//       3. else trial j + 1.  After kPqMaxTrials trials the last candidate is taken.
+// Exactness: one trial ends at neighbour x with probability min(w_x, M) / M / (deg + e 2^-32), plus
+// e 2^-32 / (deg + e 2^-32) at prev, i.e. proportional to w_x for every x.  Acceptance for
+// deg >= 2 is at least min(q, 1/q) / 2 whatever p and the degree (at most one neighbour is prev,
+// and every other one is accepted with at least min(wa, wf) / M), so the expected trials per step
+// are at most 2 max(q, 1/q) <= 32, and the cap is reached with probability < (1 - 1/32)^4096 <
+// e^-100.  With p = q = 1 every threshold is 2^32 and e = 0: trial 0 always accepts, the walk is
+// the first-order walker's.
+//
+// Membership (x in N(prev), prev in N(cur)) is a binary search in col_sorted: the rowptr of col,
+// each row ascending.  At most 32 iterations, every index clamped to [0, rowptr[V]).  The N(prev)
+// search is skipped when ta == tf (q == 1), the N(cur) search when e == 0 (p >= 1 / M); prev's
+// (begin, degree) are carried from the step before.  Candidates always come from col, so with a
+// col_sorted whose rows hold the right nodes in the wrong order the distribution is off but every
+// step is still an edge.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define COME_HD __host__ __device__
+#else
+#define COME_HD
+#endif
+
+namespace come {
+
+struct Philox {
+    uint32_t r[4];
+};
+
+COME_HD inline uint32_t mulhi32(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umulhi(a, b);
+#else
+    return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32);
+#endif
+}
+
+COME_HD inline Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+                                    uint32_t k0, uint32_t k1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 10; ++i) {
+        const uint32_t lo0 = 0xD2511F53u * c0, hi0 = mulhi32(0xD2511F53u, c0);
+        const uint32_t lo1 = 0xCD9E8D57u * c2, hi1 = mulhi32(0xCD9E8D57u, c2);
+        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+        c0 = n0;
+        c1 = lo1;
+        c2 = n2;
+        c3 = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return {{c0, c1, c2, c3}};
+}
+
+// restart iff the 24-bit uniform (r[1] >> 8) < this
+inline uint32_t walk_restart_threshold(float alpha) {
+    return (uint32_t)ceil((double)alpha * 16777216.0);
+}
+
+constexpr int kPqMaxTrials = 4096;
+constexpr int kPqSearchSteps = 32;
+constexpr float kPqMinP = 1.0f / 256.0f, kPqMaxP = 256.0f;
+constexpr float kPqMinQ = 1.0f / 16.0f, kPqMaxQ = 16.0f;
+
+struct PqParams {
+    uint64_t e;                  // outlier mass of the return edge, units of 2^-32
+    uint32_t ta, tf, tr;         // acceptance thresholds minus one: accept iff r[2] <= t
+    uint32_t restart_threshold;  // walk_restart_threshold(alpha)
+};
+
+// NaN fails both comparisons' conjunction
+inline bool pq_in_range(float p, float q) {
+    return p >= kPqMinP && p <= kPqMaxP && q >= kPqMinQ && q <= kPqMaxQ;
+}
+
+// does this (p, q) ever search col_sorted?
+inline bool pq_needs_sorted(float p, float q) { return !(q == 1.0f && p >= 1.0f); }
+
+inline uint32_t pq_threshold(double w) {  // w in (0, 1] -> round(w * 2^32) in [1, 2^32], minus 1
+    double t = floor(w * 4294967296.0 + 0.5);
+    if (!(t >= 1.0)) t = 1.0;
+    if (t > 4294967296.0) t = 4294967296.0;
+    return (uint32_t)((uint64_t)t - 1u);
+}
+
+inline PqParams pq_make_params(float alpha, float p, float q) {
+    const double wr = 1.0 / (double)p, wa = 1.0, wf = 1.0 / (double)q;
+    const double M = wa > wf ? wa : wf;
+    PqParams pp;
+    pp.ta = pq_threshold(wa / M);
+    pp.tf = pq_threshold(wf / M);
+    pp.tr = pq_threshold((wr < M ? wr : M) / M);
+    pp.e = wr > M ? (uint64_t)floor((wr - M) / M * 4294967296.0 + 0.5) : 0u;
+    pp.restart_threshold = walk_restart_threshold(alpha);
+    return pp;
+}
+
+struct PqGraph {
+    const int64_t *rowptr;
+    const int32_t *col;
+    const int32_t *col_sorted;  // may be NULL when no (p, q) search runs (pq_needs_sorted)
+    int64_t nnz;                // rowptr[V]: search indices are clamped below it
+};
+
+struct PqWalk {
+    int32_t cur, prev;  // prev = -1: none (first step, or the step after a restart)
+    int64_t pb, pdeg;   // N(prev) = col_sorted[pb, pb + pdeg)
+};
+
+// Is v in col_sorted[b, b + deg)?  A bounded binary search; an unsorted row gives some answer.
+COME_HD inline bool pq_contains(const PqGraph &g, int64_t b, int64_t deg, int32_t v) {
+    if (g.nnz <= 0) return false;
+    int64_t lo = 0, hi = deg;
+    for (int i = 0; i < kPqSearchSteps && lo < hi; ++i) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        int64_t idx = b + mid;
+        idx = idx < 0 ? 0 : idx;
+        idx = idx < g.nnz ? idx : g.nnz - 1;
+        const int32_t c = g.col_sorted[idx];
+        if (c == v) return true;
+        if (c < v)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return false;
+}
+
+// r3 * den < e * 2^32, exactly (den < 2^64, r3 < 2^32, e < 2^45: both sides below 2^96)
+COME_HD inline bool pq_outlier(uint32_t r3, uint64_t den, uint64_t e) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint64_t hi = __umul64hi((uint64_t)r3, den);
+#else
+    const uint64_t hi = (uint64_t)(((unsigned __int128)r3 * (unsigned __int128)den) >> 64);
+#endif
+    const uint64_t lo = (uint64_t)r3 * den;
+    const uint64_t ehi = e >> 32, elo = e << 32;
+    return hi < ehi || (hi == ehi && lo < elo);
+}
+
+// One step (t >= 1) of global walk gw from s.cur.  Returns the Philox blocks drawn: 0 at a node
+// without neighbours (the walk ends: alive = false, s unchanged), else 1 + the rejected trials.
+COME_HD inline uint32_t pq_step(const PqGraph &g, const PqParams &pp, int32_t start, uint32_t t,
+                                uint64_t gw, uint32_t k0, uint32_t k1, PqWalk &s, bool &alive) {
+    const int32_t cur = s.cur;
+    const int64_t b = g.rowptr[cur];
+    const int64_t deg = g.rowptr[cur + 1] - b;
+    if (deg <= 0) {  // graph_utils.py:44-45
+        alive = false;
+        return 0;
+    }
+    const uint32_t c1 = (uint32_t)gw, c2 = (uint32_t)(gw >> 32);
+    Philox x = philox4x32_10(t, c1, c2, 0u, k0, k1);
+    if ((x.r[1] >> 8) < pp.restart_threshold) {  // rand.random() < alpha (:39): restart (:42)
+        s.cur = start;
+        s.prev = -1;
+        return 1;
+    }
+    // uniform neighbour (:40): multiply-shift of a 32-bit uniform, bias <= deg / 2^32
+    uint32_t pick = (uint32_t)(((uint64_t)x.r[0] * (uint64_t)deg) >> 32);
+    const int32_t prev = s.prev;
+    uint32_t trials = 1;
+    int32_t nxt;
+    if (prev < 0 || deg == 1) {
+        nxt = g.col[b + pick];
+    } else {
+        const bool back = pp.e > 0 && pq_contains(g, b, deg, prev);
+        // by value: a select between fields of the by-reference struct becomes an indexed load
+        const uint32_t ta = pp.ta, tf = pp.tf, tr = pp.tr;
+        const bool split = ta != tf;
+        const uint64_t den = ((uint64_t)(deg < INT32_MAX ? deg : INT32_MAX) << 32) + pp.e;
+        for (;;) {
+            if (back && pq_outlier(x.r[3], den, pp.e)) {
+                nxt = prev;
+                break;
+            }
+            nxt = g.col[b + pick];
+            uint32_t thr = ta;
+            if (nxt == prev)
+                thr = tr;
+            else if (split && !pq_contains(g, s.pb, s.pdeg, nxt))
+                thr = tf;
+            if (x.r[2] <= thr || trials == (uint32_t)kPqMaxTrials) break;
+            x = philox4x32_10(t, c1, c2, trials, k0, k1);
+            pick = (uint32_t)(((uint64_t)x.r[0] * (uint64_t)deg) >> 32);
+            ++trials;
+        }
+    }
+    s.prev = cur;
+    s.pb = b;
+    s.pdeg = deg;
+    s.cur = nxt;
+    return trials;
+}
+
+}  // namespace come

@@ -22,7 +22,8 @@ Same names, arguments and outputs as the reference module, backed by libcome.so:
 
 Added for the GPU path: ``read_walk_files`` (all walk files -> one padded int64 array, natively)
 and ``device_walks`` (the HIP walker, come_random_walks: same walk distribution, Philox stream,
-walks written straight into HBM as train_o2 rows).
+walks written straight into HBM as train_o2 rows; with ``p`` / ``q`` other than 1 the node2vec
+second-order walker come_random_walks_pq, over ``sorted_adjacency``).
 
 Graph here is the minimal networkx-like object the reference's callers use: ``nodes()``,
 ``edges()`` (np.array(G.edges()) order), ``degree()`` (dict, a self-loop counts twice),
@@ -272,11 +273,28 @@ def grouper(n, iterable, padvalue=None):
     return zip_longest(*[iter(iterable)] * n, fillvalue=padvalue)
 
 
+def sorted_adjacency(rowptr, col):
+    """``col`` (CUDA int32) with each row ascending, for device_walks(..., col_sorted=): one 1-D
+    torch sort of the (row << 32) | col keys (1-D tensors only: see the gather note in
+    graph.CSRGraph.from_device_pairs)."""
+    import torch
+    V = rowptr.numel() - 1
+    row = torch.repeat_interleave(torch.arange(V, device=col.device, dtype=torch.int64),
+                                  rowptr[1:] - rowptr[:-1])
+    key = torch.sort((row << 32) | col.to(torch.int64)).values
+    return (key & 0xFFFFFFFF).to(torch.int32).contiguous()
+
+
 def device_walks(rowptr, col, starts, path_length, alpha=0.0, seed=0, walk_offset=0,
-                 emit=None, out=None):
+                 emit=None, out=None, p=1.0, q=1.0, col_sorted=None, trials_out=None):
     """HIP walker (come_random_walks): one walk per entry of ``starts`` (CUDA int32 positions);
     rowptr (CUDA int64 [V+1]) / col (CUDA int32) the CSR; returns CUDA int32 [P, path_length]
-    (``emit[position]`` per step if given, else positions; -1 after an early stop)."""
+    (``emit[position]`` per step if given, else positions; -1 after an early stop).
+    ``p``, ``q``: node2vec's return / in-out bias.  p == q == 1 is the uniform walker above;
+    anything else runs the second-order walker come_random_walks_pq (p in [2^-8, 2^8], q in
+    [2^-4, 2^4]), with ``col_sorted`` = sorted_adjacency(rowptr, col), built here when it is not
+    given (pass it to walk one graph repeatedly), and ``trials_out`` (a CUDA int64 tensor of one
+    element, or None) += the rejection trials of the launch."""
     import torch
     from ._lib import stream_handle
     for t, nm, dt in ((rowptr, "rowptr", torch.int64), (col, "col", torch.int32),
@@ -292,6 +310,23 @@ def device_walks(rowptr, col, starts, path_length, alpha=0.0, seed=0, walk_offse
         out = torch.empty((P, int(path_length)), dtype=torch.int32, device=starts.device)
     elif out.shape != (P, int(path_length)) or out.dtype != torch.int32 or not out.is_contiguous():
         raise ValueError("out must be a contiguous int32 [P, path_length] tensor")
+    if float(p) != 1.0 or float(q) != 1.0:
+        if col_sorted is None:
+            col_sorted = sorted_adjacency(rowptr, col)
+        elif not (isinstance(col_sorted, torch.Tensor) and col_sorted.is_cuda
+                  and col_sorted.dtype == torch.int32 and col_sorted.is_contiguous()
+                  and col_sorted.numel() == col.numel()):
+            raise TypeError("col_sorted must be a contiguous CUDA int32 tensor shaped like col")
+        if trials_out is not None and not (trials_out.is_cuda and trials_out.numel() == 1
+                                           and trials_out.dtype == torch.int64):
+            raise TypeError("trials_out must be a CUDA int64 tensor of one element")
+        check(_lib.lib().come_random_walks_pq(
+            ptr(rowptr), ptr(col), ptr(col_sorted), V, ptr(starts), P, int(path_length),
+            float(alpha), float(p), float(q), int(seed) & (2 ** 64 - 1), int(walk_offset),
+            None if emit is None else ptr(emit), ptr(out),
+            None if trials_out is None else ptr(trials_out), stream_handle(starts.device)),
+              "come_random_walks_pq")
+        return out
     check(_lib.lib().come_random_walks(ptr(rowptr), ptr(col), V, ptr(starts), P,
                                        int(path_length), float(alpha), int(seed) & (2 ** 64 - 1),
                                        int(walk_offset), None if emit is None else ptr(emit),

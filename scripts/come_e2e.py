@@ -2,12 +2,13 @@
 model, every phase through come_amd (no reference code), with per-phase timings and the NMI of
 the GMM communities against the planted blocks.
 
-    python scripts/come_e2e.py [--blocks 100 --block-size 1000 --dim 128 ...]
+    python scripts/come_e2e.py [--blocks 100 --block-size 1000 --dim 128 --p 1 --q 1 ...]
 
 Phases (reference file:line): walks (graph_utils.py:187-192 -> device walker), O1 pre-training
 (node_embeddings.py:35), O2 pre-training (context_embeddings.py:41), then per outer iteration
 O1 + O2 + GMM fit (community_embeddings.py:20-37, GPU EM) + community gradient
-(community_embeddings.py:61-78).  Prints one JSON line.
+(community_embeddings.py:61-78).  --p / --q: node2vec's return / in-out bias of the walks (the
+second-order device walker; the default 1, 1 is the uniform walker).  Prints one JSON line.
 """
 import argparse
 import json
@@ -23,7 +24,8 @@ sys.path.insert(0, ROOT)
 
 def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negative=5,
         window=5, walk_length=40, num_walks=5, iters=1, lr=0.025, alpha=1.0, beta=0.1,
-        com_iters=5, seed=0, reg_covar=1e-5, n_init=3, deterministic=False, log=print):
+        com_iters=5, seed=0, reg_covar=1e-5, n_init=3, deterministic=False, log=print, p=1.0,
+        q=1.0):
     import torch
     from sklearn.metrics import normalized_mutual_info_score
     from come_amd.community_embeddings import Community2Vec
@@ -49,7 +51,7 @@ def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negativ
                   device=dev)
     tick("model_s", t0)
     t0 = time.time()
-    walks = random_walks(g, num_walks, walk_length, seed=seed + 1, device=dev)
+    walks = random_walks(g, num_walks, walk_length, seed=seed + 1, device=dev, p=p, q=q)
     walks_ids = torch.where(walks >= 0, walks + 1, walks)  # rows -> node ids (ids = row + 1)
     tick("walks_s", t0)
     edges = g.edge_ids()
@@ -83,6 +85,8 @@ def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negativ
            "o2_pairs": int(pairs), "nmi": nmi,
            "gmm_converged": bool(getattr(cm.g_mixture, "converged_", False)),
            "timings_s": {k: round(v, 4) for k, v in t.items()}}
+    if p != 1.0 or q != 1.0:
+        out["walk_bias"] = {"p": p, "q": q}
     log(json.dumps(out))
     return out
 
@@ -100,10 +104,12 @@ def main():
     ap.add_argument("--num-walks", type=int, default=5)
     ap.add_argument("--iters", type=int, default=1)
     ap.add_argument("--n-init", type=int, default=3)
+    ap.add_argument("--p", type=float, default=1.0, help="node2vec return bias of the walks")
+    ap.add_argument("--q", type=float, default=1.0, help="node2vec in-out bias of the walks")
     args = ap.parse_args()
     run(blocks=args.blocks, block_size=args.block_size, p_in=args.p_in, p_out=args.p_out,
         dim=args.dim, negative=args.negative, window=args.window, walk_length=args.walk_length,
-        num_walks=args.num_walks, iters=args.iters, n_init=args.n_init)
+        num_walks=args.num_walks, iters=args.iters, n_init=args.n_init, p=args.p, q=args.q)
 
 
 if __name__ == "__main__":
