@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* ABI 5, additive: come_random_walks_pq and its CPU twin come_cpu_random_walks_pq (node2vec
+/* ABI 5, additive: come_walk_cdf, come_random_walks_w and their CPU twins come_cpu_walk_cdf,
+ * come_cpu_random_walks_w (edge-weighted walks; the unweighted walkers are unchanged).
+ * ABI 5, additive: come_random_walks_pq and its CPU twin come_cpu_random_walks_pq (node2vec
  * (p, q) second-order walks; come_random_walks is unchanged).
  * ABI 5, additive: come_gmm_estep_diag, come_gmm_diag_scratch, come_gmm_diag_moments,
  * come_gmm_diag_scatter, come_community_grad_diag and come_community_loss_diag (diagonal
@@ -428,6 +430,57 @@ int come_random_walks_pq(const int64_t *rowptr, const int32_t *col, const int32_
                          float alpha, float p, float q, uint64_t seed, int64_t walk_offset,
                          const int32_t *emit, int32_t *out, uint64_t *trials_out, void *stream);
 
+/* ---- Edge-weighted walks: a per-row CDF, built once per graph, and the walker over it ----
+ * weights: device fp32 [rowptr[V]], entry i the weight w_i >= 0 of CSR entry i.  wcdf_out: device
+ * uint32 [rowptr[V]], per entry a cumulative threshold T_i stored minus one; the walker's
+ * candidate for a 32-bit uniform r is the first entry i of the row with max(r, 1) <= wcdf[i].
+ * Per row, with wmax the row's largest weight:
+ *     u_i = llrint((double)w_i / (double)wmax * 2^32)
+ *     U_i = u_0 + ... + u_i                       exact, uint64: any order of summation
+ *     T_i = min(2^32, ceil((double)U_i / (double)U_last * 2^32)),  T_last = 2^32
+ *     wcdf[i] = T_i - 1, and 0 where T_i = 0
+ * Division, conversion and ceil are correctly rounded on both sides, so come_walk_cdf and
+ * come_cpu_walk_cdf give the same words bit for bit.  Entry i is picked for m_i = wcdf[i] -
+ * wcdf[i-1] of the 2^32 values of r (the row's "-1st" threshold taken as -1): |m_i / 2^32 - w_i /
+ * sum(w)| is a few units of 2^-32 (at most 3 + (w_i / sum w) * deg * wmax / (2 sum w): the
+ * rounding of each u_i, spread over the row).
+ * Zero mass: an entry with u_i = 0 (weight 0, or below 2^-33 of the row's largest) repeats its
+ * predecessor's threshold and is never picked.  At the head of a row there is no predecessor to
+ * repeat: such entries store 0, and the walker never selects a threshold of 0 (it searches for
+ * max(r, 1)), so they are never picked either; the value r = 0 goes to the entry that holds
+ * r = 1.  A first entry whose own mass is a single unit cedes it to its successor by the same rule.
+ * Equal weights: T_i = ceil((i + 1) / deg * 2^32), and the pick is (r * deg) >> 32, the uniform
+ * walker's, for every 32-bit r whenever deg < 2^22 (2^32 / deg then exceeds the double rounding
+ * of the quotient by far; checked on degrees up to 3,000,001).  Beyond that degree the two picks
+ * can differ for isolated r.
+ * status: device int32, set to 0 if every row was built, 1 if some weight is NaN, infinite or
+ * negative or some row of positive degree has only zero weights; wcdf_out must not be used then
+ * (such rows hold 2^32 - 1 throughout).  Rows without entries write nothing.  Asynchronous. */
+int come_walk_cdf(const int64_t *rowptr, const float *weights, int64_t V, uint32_t *wcdf_out,
+                  int32_t *status, void *stream);
+
+/* come_random_walks_pq over edge weights.  The first step of a walk, the first after a restart and
+ * any step from a node of degree 1 go to x in N(cur) with probability w(cur, x) / sum_y w(cur, y);
+ * every later step with probability proportional to w(cur, x) * beta, beta = 1/p if x == prev, 1 if
+ * x is in N(prev), 1/q otherwise.  Adjacency is what col lists whatever the weight: an entry of
+ * weight 0 is never stepped to but counts as a neighbour.  Restarts, dead ends, starts, emit, out,
+ * seed, walk_offset, the Philox counters, trials_out and the (p, q) ranges are
+ * come_random_walks_pq's; a walk depends only on (seed, walk_offset + walk, start, graph, weights,
+ * alpha, p, q).
+ *   col: device int32, ONE adjacency array, each row ascending (it serves the membership searches
+ *     too, and the return edge's mass is read at prev's index in cur's row); wcdf: come_walk_cdf's
+ *     output for the weights in that order.  Neither may be NULL.  A mis-ordered row gives wrong
+ *     probabilities but every step is still an entry of the row.
+ *   On equal weights and deg < 2^22 the walks are come_random_walks' at p = q = 1 bit for bit.
+ *   Expected trials per step: at most max(q, 1/q) * max(1, p) (256 when q >= 1 or p <= 16; 4096
+ *   in the corner p = 256, q = 1/16, reached only on rows whose mass sits almost wholly on prev);
+ *   at most max(q, 1/q) for p <= 1.  Weaker than the unweighted walker's: csrc/come_walk_pq.h.
+ * P == 0 or path_length == 0 is a no-op; a validation failure writes nothing.  Asynchronous. */
+int come_random_walks_w(const int64_t *rowptr, const int32_t *col, const uint32_t *wcdf,
+                        int64_t V, const int32_t *starts, int64_t P, int path_length, float alpha,
+                        float p, float q, uint64_t seed, int64_t walk_offset, const int32_t *emit,
+                        int32_t *out, uint64_t *trials_out, void *stream);
+
 /* Host, exact: build_deepwalk_corpus_iter (graph_utils.py:187-192) with the reference's own
  * random stream.  n_streams independent CPython random.Random streams (one per walk file of
  * write_walks_to_disk :122-146); stream s writes paths_per_stream[s] passes of V walks, streams
@@ -702,6 +755,15 @@ int come_cpu_random_walks_pq(const int64_t *rowptr, const int32_t *col, const in
                              float alpha, float p, float q, uint64_t seed, int64_t walk_offset,
                              const int32_t *emit, int32_t *out, uint64_t *trials_out,
                              int threads);
+/* come_walk_cdf and come_random_walks_w on host pointers (status_out: one host int32, written;
+ * trials_out: one host uint64, added to, or NULL): the same arithmetic and the same step body,
+ * so wcdf, status, walks and trial count are the device's bit for bit, whatever `threads`. */
+int come_cpu_walk_cdf(const int64_t *rowptr, const float *weights, int64_t V, uint32_t *wcdf_out,
+                      int32_t *status_out, int threads);
+int come_cpu_random_walks_w(const int64_t *rowptr, const int32_t *col, const uint32_t *wcdf,
+                            int64_t V, const int32_t *starts, int64_t P, int path_length,
+                            float alpha, float p, float q, uint64_t seed, int64_t walk_offset,
+                            const int32_t *emit, int32_t *out, uint64_t *trials_out, int threads);
 
 /* ---- Host helpers ---- */
 

@@ -11,6 +11,8 @@ to them.
     sgns_o2_loss(node, ctx, walks, seeds, window, negative, table) -> (total, pairs[, per walk])
     sgns_pairs_loss(inp, out, rows_in, rows_pos, rows_neg)         -> (total, counted[, per pair])
     random_walks_pq(rowptr, col, starts, path_length, alpha, p, q, seed, ...) -> walks[, trials]
+    walk_cdf(rowptr, weights)                                      -> wcdf (edge-weighted walks)
+    random_walks_w(rowptr, col, wcdf, starts, path_length, alpha, p, q, seed, ...) -> walks[, trials]
 
 Tables are updated in place (float32, C-contiguous, as the reference's numpy arrays).  ``mode``:
 MODE_HOGWILD = ``threads`` workers taking jobs of 150 walks / edges with lock-free updates, as the
@@ -231,4 +233,68 @@ def random_walks_pq(rowptr, col, starts, path_length, alpha=0.0, p=1.0, q=1.0, s
         int(path_length), float(alpha), float(p), float(q), int(seed) & (2 ** 64 - 1),
         int(walk_offset), None if emit is None else ptr(emit), ptr(out), ctypes.byref(trials),
         _threads(threads)), "come_cpu_random_walks_pq")
+    return (out, trials.value) if return_trials else out
+
+
+def sort_weighted_adjacency(rowptr, col, weights):
+    """(col, weights) with each row ascending by neighbour (numpy form of the sort inside
+    graph_utils.weighted_adjacency): one sort of the (row << 32) | col keys, the weights riding
+    along through the sort indices."""
+    _arr(rowptr, np.int64, "rowptr")
+    _arr(col, np.int32, "col")
+    _arr(weights, np.float32, "weights")
+    assert weights.shape == col.shape
+    row = np.repeat(np.arange(len(rowptr) - 1, dtype=np.int64), np.diff(rowptr))
+    key = (row << 32) | col.astype(np.int64)
+    order = np.argsort(key, kind="stable")
+    return (key[order] & 0xFFFFFFFF).astype(np.int32), np.ascontiguousarray(weights[order])
+
+
+def walk_cdf(rowptr, weights, threads=None, return_status=False):
+    """come_cpu_walk_cdf: the weighted walker's per-entry thresholds (uint32, aligned with
+    ``weights``: fp32, one per CSR entry), come_walk_cdf's bit for bit.  Raises ValueError when the
+    weights cannot be used (NaN, infinite, negative, or a row with only zeros); with
+    ``return_status`` returns ``(wcdf, status)`` instead of raising."""
+    _arr(rowptr, np.int64, "rowptr")
+    _arr(weights, np.float32, "weights")
+    assert weights.shape == (int(rowptr[-1]),)
+    wcdf = np.zeros(len(weights), np.uint32)
+    status = ctypes.c_int32(0)
+    check(_lib.lib().come_cpu_walk_cdf(ptr(rowptr), ptr(weights), len(rowptr) - 1, ptr(wcdf),
+                                       ctypes.byref(status), _threads(threads)),
+          "come_cpu_walk_cdf")
+    if return_status:
+        return wcdf, status.value
+    if status.value:
+        raise ValueError("edge weights must be finite and >= 0, with a positive weight in every "
+                         "row that has entries")
+    return wcdf
+
+
+def random_walks_w(rowptr, col, wcdf, starts, path_length, alpha=0.0, p=1.0, q=1.0, seed=0,
+                   walk_offset=0, emit=None, out=None, return_trials=False, threads=None):
+    """come_cpu_random_walks_w: edge-weighted node2vec (p, q) walks, the device walker's
+    (graph_utils.device_walks(..., weights=)) bit for bit.  ``col``: each row ascending; ``wcdf``:
+    walk_cdf of the weights in that order (sort_weighted_adjacency gives both from any order).
+    Returns and ``return_trials`` as random_walks_pq."""
+    _arr(rowptr, np.int64, "rowptr")
+    _arr(col, np.int32, "col")
+    _arr(wcdf, np.uint32, "wcdf")
+    _arr(starts, np.int32, "starts")
+    assert wcdf.shape == col.shape
+    V, P = len(rowptr) - 1, len(starts)
+    if emit is not None:
+        _arr(emit, np.int32, "emit")
+        assert emit.shape == (V,)
+    if out is None:
+        out = np.empty((P, int(path_length)), np.int32)
+    else:
+        _arr(out, np.int32, "out", True)
+        assert out.shape == (P, int(path_length))
+    trials = ctypes.c_uint64(0)
+    check(_lib.lib().come_cpu_random_walks_w(
+        ptr(rowptr), ptr(col), ptr(wcdf), V, ptr(starts), P, int(path_length), float(alpha),
+        float(p), float(q), int(seed) & (2 ** 64 - 1), int(walk_offset),
+        None if emit is None else ptr(emit), ptr(out), ctypes.byref(trials), _threads(threads)),
+        "come_cpu_random_walks_w")
     return (out, trials.value) if return_trials else out

@@ -27,6 +27,8 @@
 //   come_cpu_random_walks_pq the node2vec (p, q) walker: come_walk_pq.h's step body, which the
 //                            kernel k_random_walks_pq compiles too, so the walks are the device's
 //                            bit for bit; walks split over the threads.
+//   come_cpu_walk_cdf / come_cpu_random_walks_w  edge-weighted walks: the same header's CDF
+//                            arithmetic and pq_step<true>, as k_walk_cdf / k_random_walks_w.
 // Each compute body is built twice, for AVX2+FMA and for the baseline ISA (explicit fmaf either
 // way, -ffp-contract=off: identical results), and the first call picks one from the CPU.
 #include <stdint.h>
@@ -695,7 +697,7 @@ extern "C" int come_cpu_random_walks_pq(const int64_t *rowptr, const int32_t *co
     if (!col_sorted && pq_needs_sorted(p, q))
         return set_error(COME_E_INVALID,
                          "cpu_random_walks_pq: col_sorted may be NULL only with q == 1 and p >= 1");
-    const PqGraph g{rowptr, col, col_sorted, rowptr[V]};
+    const PqGraph g{rowptr, col, col_sorted, rowptr[V], nullptr};
     const PqParams pp = pq_make_params(alpha, p, q);
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     std::atomic<uint64_t> total(0);
@@ -709,6 +711,93 @@ extern "C" int come_cpu_random_walks_pq(const int64_t *rowptr, const int32_t *co
             PqWalk s{alive ? start : -1, -1, 0, 0};
             for (int t = 0; t < L; ++t) {
                 if (alive && t > 0) trials += pq_step(g, pp, start, (uint32_t)t, gw, k0, k1, s, alive);
+                row[t] = alive ? (emit ? emit[s.cur] : s.cur) : -1;
+            }
+        }
+        total += trials;
+    });
+    if (trials_out) *trials_out += total.load();
+    return COME_OK;
+}
+
+// come_walk_cdf on host memory: come_walk_pq.h's cdf_units / cdf_threshold, row by row.  The
+// prefix sums are integers and the maximum does not depend on an order, so this is the kernel's
+// wcdf bit for bit, whatever its split of rows over lanes and wavefronts or `threads` here.
+extern "C" int come_cpu_walk_cdf(const int64_t *rowptr, const float *weights, int64_t V,
+                                 uint32_t *wcdf_out, int32_t *status_out, int threads) {
+    using namespace come;
+    if (V <= 0 || V > INT32_MAX)
+        return set_error(COME_E_INVALID, "cpu_walk_cdf: V must be in [1, 2^31)");
+    int rc = check_threads(threads);
+    if (rc) return rc;
+    if (!rowptr || !weights || !wcdf_out || !status_out)
+        return set_error(COME_E_INVALID, "cpu_walk_cdf: null pointer");
+    const int64_t nnz = rowptr[V];
+    std::atomic<int32_t> status(0);
+    parallel_rows(V, threads, [&](int64_t lo, int64_t hi) {
+        for (int64_t v = lo; v < hi; ++v) {
+            const int64_t b = rowptr[v], deg = rowptr[v + 1] - b;
+            if (b < 0 || deg <= 0 || b + deg > nnz) continue;  // empty, or not a CSR
+            float wmax = 0.0f;
+            bool ok = true;
+            for (int64_t i = 0; i < deg; ++i) {
+                const float x = weights[b + i];
+                ok = ok && cdf_weight_ok(x);
+                wmax = x > wmax ? x : wmax;
+            }
+            if (!ok || !(wmax > 0.0f)) {
+                for (int64_t i = 0; i < deg; ++i) wcdf_out[b + i] = 0xFFFFFFFFu;
+                status = 1;
+                continue;
+            }
+            uint64_t total = 0, U = 0;
+            for (int64_t i = 0; i < deg; ++i) total += cdf_units(weights[b + i], wmax);
+            for (int64_t i = 0; i < deg; ++i) {
+                U += cdf_units(weights[b + i], wmax);
+                wcdf_out[b + i] = cdf_threshold(U, total);
+            }
+        }
+    });
+    *status_out = status.load();
+    return COME_OK;
+}
+
+// The weighted walker on host memory: pq_step<true>, the kernel's own step body.
+extern "C" int come_cpu_random_walks_w(const int64_t *rowptr, const int32_t *col,
+                                       const uint32_t *wcdf, int64_t V, const int32_t *starts,
+                                       int64_t P, int L, float alpha, float p, float q,
+                                       uint64_t seed, int64_t walk_offset, const int32_t *emit,
+                                       int32_t *out, uint64_t *trials_out, int threads) {
+    using namespace come;
+    if (V <= 0 || V > INT32_MAX)
+        return set_error(COME_E_INVALID, "cpu_random_walks_w: V must be in [1, 2^31)");
+    if (P < 0 || L < 0 || walk_offset < 0)
+        return set_error(COME_E_INVALID, "cpu_random_walks_w: P, L and walk_offset must be >= 0");
+    if (!(alpha >= 0.0f && alpha <= 1.0f))
+        return set_error(COME_E_INVALID, "cpu_random_walks_w: alpha not in [0,1]");
+    if (!pq_in_range(p, q))
+        return set_error(COME_E_INVALID,
+                         "cpu_random_walks_w: p must be in [2^-8, 2^8] and q in [2^-4, 2^4]");
+    int rc = check_threads(threads);
+    if (rc) return rc;
+    if (P == 0 || L == 0) return COME_OK;
+    if (!rowptr || !col || !wcdf || !starts || !out)
+        return set_error(COME_E_INVALID, "cpu_random_walks_w: null pointer");
+    const PqGraph g{rowptr, col, col, rowptr[V], wcdf};
+    const PqParams pp = pq_make_params(alpha, p, q);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    std::atomic<uint64_t> total(0);
+    parallel_rows(P, threads, [&](int64_t lo, int64_t hi) {
+        uint64_t trials = 0;
+        for (int64_t w = lo; w < hi; ++w) {
+            int32_t *row = out + w * (int64_t)L;
+            const int32_t start = starts[w];
+            const uint64_t gw = (uint64_t)(walk_offset + w);
+            bool alive = start >= 0 && start < V;  // not a node: an empty walk
+            PqWalk s{alive ? start : -1, -1, 0, 0};
+            for (int t = 0; t < L; ++t) {
+                if (alive && t > 0)
+                    trials += pq_step<true>(g, pp, start, (uint32_t)t, gw, k0, k1, s, alive);
                 row[t] = alive ? (emit ? emit[s.cur] : s.cur) : -1;
             }
         }

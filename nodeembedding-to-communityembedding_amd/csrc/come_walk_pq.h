@@ -1,6 +1,7 @@
 // come_walk_pq.h -- the walkers' random stream (Philox-4x32-10) and the node2vec (p, q)
-// second-order step: one copy, compiled as device code by come_walk.hip / come_walk_pq.hip and as
-// plain host C++ by come_cpu.cpp (the CPU twin), so the two are the same walks bit for bit.
+// second-order step: one copy, compiled as device code by come_walk.hip / come_walk_pq.hip /
+// come_walk_w.hip and as plain host C++ by come_cpu.cpp (the CPU twins), so the two are the same
+// walks bit for bit.
 //
 // Semantics.  A walk is c_0 = start.  Its first step, and the first step after a restart, is
 // uniform over N(c_0): the first-order walker's step (come_walk.hip), same Philox block, same
@@ -45,6 +46,45 @@
 // (begin, degree) are carried from the step before.  Candidates always come from col, so with a
 // col_sorted whose rows hold the right nodes in the wrong order the distribution is off but every
 // step is still an edge.
+//
+// Edge weights (pq_step<true>, come_random_walks_w).  The same step with two substitutions; the
+// Philox blocks, the thresholds ta / tf / tr and the outlier test are the code above.  Entry i of
+// a row carries a 32-bit cumulative threshold wcdf[b + i] (come_walk_cdf builds them, cdf_units /
+// cdf_threshold below are its arithmetic), and the search of r[0] in it replaces the multiply-shift
+// pick: the candidate is the first i with max(r[0], 1) <= wcdf[b + i], a lower-bound search of at
+// most kPqSearchSteps iterations with indices clamped to [0, nnz).  Write m_i for the number of
+// 32-bit values of r[0] that end at i (pq_wmass); sum_i m_i = 2^32, an entry of weight 0 has
+// m_i = 0, and with H = max(wcdf[i] + 1, 1), L = max(wcdf[i-1] + 1, 1) (L = 1 for i = 0)
+// m_i = H - L + (L == 1 && H >= 2): the draw 0 counts as 1, so a threshold 0 at the head of a row
+// -- entries of weight 0 before the first positive one -- is never selected.
+//     no prev, or deg(cur) == 1: the candidate is taken: probability m_x / 2^32.
+//     otherwise, with E' = floor(m_prev e / 2^32) (a 96-bit product; 0 when prev is not in the row):
+//       1. if E' > 0: return to prev iff r[3] * (2^32 + E') < E' * 2^32   (pq_outlier; E' < 2^45);
+//       2. else the candidate x is taken iff r[2] <= t(x) - 1;  3. else the next trial, capped.
+// Exactness: one trial ends at x != prev with probability 2^32 / (2^32 + E') * m_x / 2^32 *
+// t(x) / 2^32 = m_x t(x) / (2^32 (2^32 + E')), and at prev with (E' 2^32 + m_prev tr) / (2^32 (2^32
+// + E')) = m_prev (e + tr) / (2^32 (2^32 + E')) up to the floor in E' (less than 2^-32 of a trial).
+// t(x) / 2^32 = min(beta_x, M) / M and (e + tr) / 2^32 = (1/p) / M, so a trial ends at x with
+// probability proportional to m_x beta_x for every x, prev included.  With equal weights m_i is
+// the multiply-shift pick's count (come.h, come_walk_cdf), so candidates and acceptances are
+// pq_step<false>'s and at p = q = 1 the walks are come_random_walks' bit for bit.  With e > 0 the
+// outlier probability E' / (2^32 + E') equals e / (deg 2^32 + e) only to within e 2^-64 (m_prev is
+// 2^32 / deg rounded to an integer), so on equal weights the walks at p < 1 / M are
+// come_random_walks_pq's except where r[3] falls between the two, fewer than 2^-24 of the steps;
+// tests pin them equal on the test graphs.
+// Acceptance is WEAKER than above.  prev can hold almost all of a row's mass, so "at most one
+// neighbour is prev" bounds nothing: with f = m_prev / 2^32 a trial succeeds with probability at
+// least f tr' + (1 - f) min(ta, tf) / 2^32 where tr' = tr / 2^32 = min(1/p, M) / M, and for f -> 1
+// only min(ta, tf, tr) / 2^32 remains.  That is min(1/q, 1, 1/p) / max(1, 1/q): at least 2^-8
+// whenever q >= 1 or p <= 16, i.e. at most 256 expected trials, the cap reached with probability
+// < (1 - 2^-8)^4096 < e^-16; in the corner p > 16 and q < 1 it falls to 2^-12 at (256, 1/16),
+// 4096 expected trials, and there the cap can be reached with probability up to e^-1 on a row whose
+// mass sits on prev (the last candidate is then taken: prev, almost surely).  For p <= 1 the
+// bound is min(q, 1/q) whatever the weights, twice the unweighted walker's.
+// Rows must be ascending: the outlier needs prev's INDEX in cur's row to read m_prev, so the
+// weighted entry points take one adjacency array, each row ascending, with wcdf in that order; the
+// membership search returns the index and there is no separate col_sorted.  A mis-ordered row
+// gives wrong probabilities, but every step is still an entry of the row.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -136,6 +176,7 @@ struct PqGraph {
     const int32_t *col;
     const int32_t *col_sorted;  // may be NULL when no (p, q) search runs (pq_needs_sorted)
     int64_t nnz;                // rowptr[V]: search indices are clamped below it
+    const uint32_t *wcdf;       // pq_step<true> only: per-entry thresholds, col's rows ascending
 };
 
 struct PqWalk {
@@ -143,9 +184,10 @@ struct PqWalk {
     int64_t pb, pdeg;   // N(prev) = col_sorted[pb, pb + pdeg)
 };
 
-// Is v in col_sorted[b, b + deg)?  A bounded binary search; an unsorted row gives some answer.
-COME_HD inline bool pq_contains(const PqGraph &g, int64_t b, int64_t deg, int32_t v) {
-    if (g.nnz <= 0) return false;
+// v's index in col_sorted[b, b + deg), or -1.  A bounded binary search; an unsorted row gives some
+// answer.
+COME_HD inline int64_t pq_index(const PqGraph &g, int64_t b, int64_t deg, int32_t v) {
+    if (g.nnz <= 0) return -1;
     int64_t lo = 0, hi = deg;
     for (int i = 0; i < kPqSearchSteps && lo < hi; ++i) {
         const int64_t mid = lo + ((hi - lo) >> 1);
@@ -153,13 +195,76 @@ COME_HD inline bool pq_contains(const PqGraph &g, int64_t b, int64_t deg, int32_
         idx = idx < 0 ? 0 : idx;
         idx = idx < g.nnz ? idx : g.nnz - 1;
         const int32_t c = g.col_sorted[idx];
-        if (c == v) return true;
+        if (c == v) return mid;
         if (c < v)
             lo = mid + 1;
         else
             hi = mid;
     }
-    return false;
+    return -1;
+}
+
+COME_HD inline bool pq_contains(const PqGraph &g, int64_t b, int64_t deg, int32_t v) {
+    return pq_index(g, b, deg, v) >= 0;
+}
+
+// ---- edge weights: the per-row CDF's arithmetic (come_walk_cdf) and its search ----
+
+// u_i: the weight in units of 2^-32 of the row's largest.  The division is correctly rounded and
+// the scaling exact, so the device and the host agree (nothing here is built with fast-math).
+COME_HD inline uint64_t cdf_units(float w, float wmax) {
+    return (uint64_t)llrint((double)w / (double)wmax * 4294967296.0);
+}
+
+// T_i - 1 (saturating at 0) from the exact prefix sum U_i and the row's total U_last > 0
+COME_HD inline uint32_t cdf_threshold(uint64_t U, uint64_t Ulast) {
+    double t = ceil((double)U / (double)Ulast * 4294967296.0);
+    if (U >= Ulast || t > 4294967296.0) t = 4294967296.0;
+    const uint64_t T = (uint64_t)t;
+    return (uint32_t)(T > 0 ? T - 1 : 0);
+}
+
+// finite and >= 0 (NaN fails the comparison)
+COME_HD inline bool cdf_weight_ok(float w) { return w >= 0.0f && w <= 3.4028234663852886e38f; }
+
+COME_HD inline uint32_t pq_wcdf_at(const PqGraph &g, int64_t idx) {
+    idx = idx < 0 ? 0 : idx;
+    idx = idx < g.nnz ? idx : g.nnz - 1;
+    return g.wcdf[idx];
+}
+
+// The first i in [0, deg) with max(r0, 1) <= wcdf[b + i]; deg - 1 if there is none (a row whose
+// last threshold is not 2^32 - 1: not come_walk_cdf's).  deg >= 1, nnz >= 1.
+COME_HD inline int64_t pq_wpick(const PqGraph &g, int64_t b, int64_t deg, uint32_t r0) {
+    r0 |= (uint32_t)(r0 == 0);
+    int64_t lo = 0, hi = deg - 1;
+    for (int i = 0; i < kPqSearchSteps && lo < hi; ++i) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (r0 <= pq_wcdf_at(g, b + mid))
+            hi = mid;
+        else
+            lo = mid + 1;
+    }
+    return lo;
+}
+
+// m_i: how many of the 2^32 values of r0 pq_wpick sends to entry i of the row at b
+COME_HD inline uint64_t pq_wmass(const PqGraph &g, int64_t b, int64_t i) {
+    uint64_t H = (uint64_t)pq_wcdf_at(g, b + i) + 1u;
+    uint64_t L = i > 0 ? (uint64_t)pq_wcdf_at(g, b + i - 1) + 1u : 1u;
+    L = L < 1u ? 1u : L;
+    H = H < L ? L : H;  // a threshold array that is not monotone: no mass
+    return H - L + (uint64_t)(L == 1u && H >= 2u);
+}
+
+// floor(m * e / 2^32), m <= 2^32, e < 2^45: a 96-bit product
+COME_HD inline uint64_t pq_scale_outlier(uint64_t m, uint64_t e) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint64_t hi = __umul64hi(m, e);
+#else
+    const uint64_t hi = (uint64_t)(((unsigned __int128)m * (unsigned __int128)e) >> 64);
+#endif
+    return (hi << 32) | ((m * e) >> 32);
 }
 
 // r3 * den < e * 2^32, exactly (den < 2^64, r3 < 2^32, e < 2^45: both sides below 2^96)
@@ -174,8 +279,21 @@ COME_HD inline bool pq_outlier(uint32_t r3, uint64_t den, uint64_t e) {
     return hi < ehi || (hi == ehi && lo < elo);
 }
 
+// The candidate's index in the row for the draw r0: by weight (the CDF search), or uniform (:40):
+// multiply-shift of a 32-bit uniform, bias <= deg / 2^32
+template <bool W>
+COME_HD inline int64_t pq_pick(const PqGraph &g, int64_t b, int64_t deg, uint32_t r0) {
+    if constexpr (W)
+        return pq_wpick(g, b, deg, r0);
+    else
+        return (int64_t)(((uint64_t)r0 * (uint64_t)deg) >> 32);
+}
+
 // One step (t >= 1) of global walk gw from s.cur.  Returns the Philox blocks drawn: 0 at a node
 // without neighbours (the walk ends: alive = false, s unchanged), else 1 + the rejected trials.
+// W: edge weights -- candidates by pq_wpick in g.wcdf, the outlier mass scaled by prev's mass;
+// g.col == g.col_sorted then, each row ascending.
+template <bool W = false>
 COME_HD inline uint32_t pq_step(const PqGraph &g, const PqParams &pp, int32_t start, uint32_t t,
                                 uint64_t gw, uint32_t k0, uint32_t k1, PqWalk &s, bool &alive) {
     const int32_t cur = s.cur;
@@ -192,21 +310,29 @@ COME_HD inline uint32_t pq_step(const PqGraph &g, const PqParams &pp, int32_t st
         s.prev = -1;
         return 1;
     }
-    // uniform neighbour (:40): multiply-shift of a 32-bit uniform, bias <= deg / 2^32
-    uint32_t pick = (uint32_t)(((uint64_t)x.r[0] * (uint64_t)deg) >> 32);
+    int64_t pick = pq_pick<W>(g, b, deg, x.r[0]);
     const int32_t prev = s.prev;
     uint32_t trials = 1;
     int32_t nxt;
     if (prev < 0 || deg == 1) {
         nxt = g.col[b + pick];
     } else {
-        const bool back = pp.e > 0 && pq_contains(g, b, deg, prev);
+        bool back;
+        uint64_t e = pp.e, den;
+        if constexpr (W) {
+            const int64_t at = e > 0 ? pq_index(g, b, deg, prev) : -1;
+            e = at >= 0 ? pq_scale_outlier(pq_wmass(g, b, at), e) : 0u;
+            back = e > 0;
+            den = 4294967296ull + e;
+        } else {
+            back = e > 0 && pq_contains(g, b, deg, prev);
+            den = ((uint64_t)(deg < INT32_MAX ? deg : INT32_MAX) << 32) + e;
+        }
         // by value: a select between fields of the by-reference struct becomes an indexed load
         const uint32_t ta = pp.ta, tf = pp.tf, tr = pp.tr;
         const bool split = ta != tf;
-        const uint64_t den = ((uint64_t)(deg < INT32_MAX ? deg : INT32_MAX) << 32) + pp.e;
         for (;;) {
-            if (back && pq_outlier(x.r[3], den, pp.e)) {
+            if (back && pq_outlier(x.r[3], den, e)) {
                 nxt = prev;
                 break;
             }
@@ -218,7 +344,7 @@ COME_HD inline uint32_t pq_step(const PqGraph &g, const PqParams &pp, int32_t st
                 thr = tf;
             if (x.r[2] <= thr || trials == (uint32_t)kPqMaxTrials) break;
             x = philox4x32_10(t, c1, c2, trials, k0, k1);
-            pick = (uint32_t)(((uint64_t)x.r[0] * (uint64_t)deg) >> 32);
+            pick = pq_pick<W>(g, b, deg, x.r[0]);
             ++trials;
         }
     }

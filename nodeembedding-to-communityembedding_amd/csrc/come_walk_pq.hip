@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(WALK_PQ_BLOCK) k_random_walks_pq(WalkPqArgs a)
     const int64_t w = w0 + tid;
     const uint64_t gw = (uint64_t)(a.walk_offset + w);
     const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
-    const PqGraph g{a.rowptr, a.col, a.col_sorted, a.rowptr[a.V]};
+    const PqGraph g{a.rowptr, a.col, a.col_sorted, a.rowptr[a.V], nullptr};
     int32_t start = -1;
     if (w < a.P) start = a.starts[w];
     bool alive = start >= 0 && start < a.V;  // not a node: an empty walk

@@ -6,7 +6,10 @@ truncated walk with restart ``__random_walk__`` (:20-46) and ``build_deepwalk_co
 generated for whole batches at once on the device from a CSR adjacency (uniform neighbour choice,
 restart probability alpha, a walk stops at a node without neighbours; HIP kernel
 come_random_walks) -- same distribution as the reference walker, not the same random stream.  The
-reference's exact stream (CPython random.Random) is graph_utils.build_deepwalk_corpus.
+reference's exact stream (CPython random.Random) is graph_utils.build_deepwalk_corpus.  A
+``CSRGraph`` may carry edge weights; its walks then step in proportion to them
+(come_random_walks_w), and ``degree_by_id(weighted=True)`` gives the strengths a model of such a
+corpus should be built from.
 
 Synthetic generators for the benchmark configurations: ``chung_lu`` (power-law
 expected degrees) and ``sbm`` (stochastic block model).  Node ids are 1..V (row = id - 1).
@@ -15,15 +18,30 @@ import numpy as np
 
 
 class CSRGraph(object):
-    """Undirected simple graph in CSR form over rows 0..V-1 (node id = row + 1)."""
+    """Undirected simple graph in CSR form over rows 0..V-1 (node id = row + 1).  ``weights``
+    (one per edge row, optional): ``.weights`` is float32 aligned with ``.col``, the same on both
+    directions of an edge, and ``.strength`` float64 [V] the sum per node; for a pair listed more
+    than once the last listing wins (nx.Graph.add_weighted_edges_from).  Without weights
+    ``.weights`` is None and ``.strength`` the degree."""
 
-    def __init__(self, V, edges_rows):
+    weights = None
+
+    def __init__(self, V, edges_rows, weights=None):
         self.V = int(V)
         e = np.asarray(edges_rows, np.int64).reshape(-1, 2)
-        e = e[e[:, 0] != e[:, 1]]
+        loop = e[:, 0] == e[:, 1]
+        e = e[~loop]
         a = np.minimum(e[:, 0], e[:, 1])
         b = np.maximum(e[:, 0], e[:, 1])
-        key = np.unique(a * V + b)
+        if weights is None:
+            key = np.unique(a * V + b)
+        else:
+            w = np.asarray(weights, np.float32).reshape(-1)
+            if len(w) != len(loop):
+                raise ValueError("weights must hold one value per edge row")
+            w = w[~loop]
+            key, last = np.unique((a * V + b)[::-1], return_index=True)  # last listing wins
+            w = w[::-1][last]
         a, b = key // V, key % V
         self.edges = np.stack([a, b], axis=1)  # unique undirected edges (rows)
         src = np.concatenate([a, b])
@@ -33,6 +51,15 @@ class CSRGraph(object):
         self.degree = np.bincount(src, minlength=V).astype(np.int64)
         self.rowptr = np.zeros(V + 1, np.int64)
         np.cumsum(self.degree, out=self.rowptr[1:])
+        if weights is not None:
+            self.weights = np.ascontiguousarray(np.concatenate([w, w])[order])
+
+    @property
+    def strength(self):
+        if self.weights is None:
+            return self.degree.astype(np.float64)
+        return np.bincount(np.repeat(np.arange(self.V), self.degree),
+                           self.weights.astype(np.float64), minlength=self.V)
 
     @classmethod
     def from_device_pairs(cls, V, u, v):
@@ -72,9 +99,12 @@ class CSRGraph(object):
     def num_edges(self):
         return len(self.edges)
 
-    def degree_by_id(self):
-        """(ids, degrees) as Model(nodes_degree=...) accepts (G.degree() of the reference)."""
-        return np.arange(1, self.V + 1, dtype=np.int64), self.degree.copy()
+    def degree_by_id(self, weighted=False):
+        """(ids, degrees) as Model(nodes_degree=...) accepts (G.degree() of the reference);
+        ``weighted``: (ids, strengths) -- the visit rate of a weighted walk follows strength, so
+        a weighted corpus's negative table, hot rows and quiet rows should be built from these."""
+        ids = np.arange(1, self.V + 1, dtype=np.int64)
+        return (ids, self.strength) if weighted else (ids, self.degree.copy())
 
     def edge_ids(self):
         """[E, 2] node ids (np.array(G.edges()) of the reference)."""
@@ -143,7 +173,7 @@ def sbm(blocks, block_size, p_in, p_out, seed=0):
 
 
 def random_walks(g, num_paths, path_length, alpha=0.0, seed=0, device="cuda", starts=None,
-                 walk_offset=0, p=1.0, q=1.0):
+                 walk_offset=0, p=1.0, q=1.0, weighted=None):
     """Walks [num_paths * V, path_length] of ROW indices (int32 tensor on `device`), -1 after a
     walk stops.  Per pass the start nodes are a fresh permutation of all nodes (graph_utils.py:
     187-192); the walks themselves come from the HIP walker (come_random_walks: uniform
@@ -151,7 +181,9 @@ def random_walks(g, num_paths, path_length, alpha=0.0, seed=0, device="cuda", st
     With ``starts`` given (one walk per entry), ``walk_offset`` is the global index of its first
     walk: a shard [lo, hi) of a corpus generated with starts[lo:hi], walk_offset=lo equals rows
     lo..hi-1 of the whole corpus.  ``p``, ``q``: node2vec's return / in-out bias (other than 1:
-    the second-order walker come_random_walks_pq, see graph_utils.device_walks)."""
+    the second-order walker come_random_walks_pq, see graph_utils.device_walks).  ``weighted``:
+    step with probability proportional to the edge weights (come_random_walks_w); None means
+    "if ``g.weights`` is set"."""
     import torch
     from .graph_utils import device_walks
     dev = torch.device(device)
@@ -163,5 +195,11 @@ def random_walks(g, num_paths, path_length, alpha=0.0, seed=0, device="cuda", st
         starts = torch.cat([torch.randperm(g.V, generator=gen, device=dev)
                             for _ in range(num_paths)])
     starts = torch.as_tensor(starts, device=dev).to(torch.int32).contiguous()
+    w = getattr(g, "weights", None)
+    if weighted is None:
+        weighted = w is not None
+    if weighted and w is None:
+        raise ValueError("weighted=True needs a graph with weights")
+    w = torch.from_numpy(np.ascontiguousarray(w, np.float32)).to(dev) if weighted else None
     return device_walks(rowptr, col, starts, path_length, alpha=alpha, seed=seed,
-                        walk_offset=walk_offset, p=p, q=q)
+                        walk_offset=walk_offset, p=p, q=q, weights=w)

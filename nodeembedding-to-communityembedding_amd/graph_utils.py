@@ -23,7 +23,9 @@ Same names, arguments and outputs as the reference module, backed by libcome.so:
 Added for the GPU path: ``read_walk_files`` (all walk files -> one padded int64 array, natively)
 and ``device_walks`` (the HIP walker, come_random_walks: same walk distribution, Philox stream,
 walks written straight into HBM as train_o2 rows; with ``p`` / ``q`` other than 1 the node2vec
-second-order walker come_random_walks_pq, over ``sorted_adjacency``).
+second-order walker come_random_walks_pq, over ``sorted_adjacency``; with ``weights`` the
+edge-weighted walker come_random_walks_w, over ``weighted_adjacency``), and
+``load_weighted_edgelist`` (lines ``u v w`` -> a Graph with ``.weights``).
 
 Graph here is the minimal networkx-like object the reference's callers use: ``nodes()``,
 ``edges()`` (np.array(G.edges()) order), ``degree()`` (dict, a self-loop counts twice),
@@ -51,12 +53,31 @@ class Graph(object):
         self.col = col                # int32 [nnz]: neighbour positions, insertion order
         self.degree_arr = degree      # int64 [V]: G.degree() values
         self.edge_pos = edge_pos      # int32 [E, 2]: G.edges() as positions
+        self.weights = None           # float32 [nnz] aligned with col, or None: unweighted
         self._pos = None
 
     @staticmethod
-    def from_edges(edges):
-        """nx.Graph().add_edges_from(edges) for an [E, 2] array of node ids (file order)."""
+    def from_edges(edges, weights=None):
+        """nx.Graph().add_edges_from(edges) for an [E, 2] array of node ids (file order).  With
+        ``weights`` ([E]): add_weighted_edges_from -- ``.weights`` is float32 aligned with ``.col``,
+        the same on both directions of an edge; for a pair listed more than once the last listing
+        wins."""
         e = np.ascontiguousarray(np.asarray(edges, np.int64).reshape(-1, 2))
+        if weights is not None:
+            G = Graph.from_edges(e)
+            w = np.asarray(weights, np.float32).reshape(-1)
+            if len(w) != len(e):
+                raise ValueError("weights must hold one value per edge row")
+            V = len(G.node_ids)
+            pos = G.positions_of(e.ravel()).reshape(-1, 2) if len(e) else e
+            key = np.minimum(pos[:, 0], pos[:, 1]) * V + np.maximum(pos[:, 0], pos[:, 1])
+            uk, first_rev = np.unique(key[::-1], return_index=True)  # last listing wins
+            uw = w[::-1][first_rev]
+            row = np.repeat(np.arange(V, dtype=np.int64), np.diff(G.rowptr))
+            c = G.col.astype(np.int64)
+            G.weights = np.ascontiguousarray(
+                uw[np.searchsorted(uk, np.minimum(row, c) * V + np.maximum(row, c))])
+            return G
         E = len(e)
         cap = max(2 * E, 1)
         node_ids = np.empty(cap, np.int64)
@@ -82,8 +103,19 @@ class Graph(object):
     def degree(self):
         return dict(zip(self.node_ids.tolist(), self.degree_arr.tolist()))
 
-    def degree_by_id(self):
+    def degree_by_id(self, weighted=False):
+        """(ids, degrees); ``weighted``: (ids, strengths), the sums of each node's weights."""
+        if weighted:
+            return self.node_ids.copy(), self.strength
         return self.node_ids.copy(), self.degree_arr.copy()
+
+    @property
+    def strength(self):
+        """float64 [V]: the sum of the weights of each node's entries (its degree if unweighted)."""
+        if self.weights is None:
+            return np.diff(self.rowptr).astype(np.float64)
+        row = np.repeat(np.arange(len(self.node_ids)), np.diff(self.rowptr))
+        return np.bincount(row, self.weights.astype(np.float64), minlength=len(self.node_ids))
 
     def positions_of(self, ids):
         if self._pos is None:
@@ -120,8 +152,11 @@ class Graph(object):
         k = np.arange(len(self.col), dtype=np.int64) - np.repeat(self.rowptr[:-1], deg)
         key = np.where(self.col < row, self.col.astype(np.int64), V + k)
         order = np.lexsort((key, row))
-        return Graph(self.node_ids.copy(), self.rowptr.copy(), self.col[order].copy(),
-                     self.degree_arr.copy(), self.edge_pos.copy())
+        G = Graph(self.node_ids.copy(), self.rowptr.copy(), self.col[order].copy(),
+                  self.degree_arr.copy(), self.edge_pos.copy())
+        if self.weights is not None:
+            G.weights = self.weights[order].copy()
+        return G
 
 
 def load_adjacencylist(file_, undirected=False, chunksize=10000):
@@ -134,6 +169,23 @@ def load_adjacencylist(file_, undirected=False, chunksize=10000):
                                                                            rows.shape[1]))
     G = Graph.from_edges(rows)
     return G.to_undirected() if undirected else G
+
+
+def load_weighted_edgelist(file_):
+    """Lines ``u v w`` (integer node ids, a float weight; '#' comments, blank lines skipped) ->
+    Graph.from_edges(edges, weights): an undirected graph with ``.weights``."""
+    edges, weights = [], []
+    with open(file_) as f:
+        for n, line in enumerate(f, 1):
+            t = line.split("#", 1)[0].split()
+            if not t:
+                continue
+            if len(t) != 3:
+                raise ValueError("%s:%d: expected 'u v w'" % (file_, n))
+            edges.append((int(t[0]), int(t[1])))
+            weights.append(float(t[2]))
+    return Graph.from_edges(np.array(edges, np.int64).reshape(-1, 2),
+                            np.array(weights, np.float32))
 
 
 def read_int_rows(path, width=None):
@@ -285,8 +337,45 @@ def sorted_adjacency(rowptr, col):
     return (key & 0xFFFFFFFF).to(torch.int32).contiguous()
 
 
+def _gather_1d(t, idx, step=1 << 24):
+    """t[idx] for 1-D CUDA tensors, in slices of 2^24 indices (see the gather note in
+    graph.CSRGraph.from_device_pairs)."""
+    import torch
+    if idx.numel() <= step:
+        return t[idx].contiguous()
+    return torch.cat([t[idx[i:i + step]] for i in range(0, idx.numel(), step)])
+
+
+def weighted_adjacency(rowptr, col, weights):
+    """``(col_sorted, wcdf)`` for device_walks(..., wadj=): ``col`` (CUDA int32) with each row
+    ascending and come_walk_cdf's thresholds (CUDA int32 holding the uint32 words) of ``weights``
+    (CUDA float32, aligned with col) in that order.  One 1-D key sort as sorted_adjacency, the
+    weights riding along through the sort indices.  ValueError when the weights cannot be used
+    (NaN, infinite, negative, or a row with only zeros)."""
+    import torch
+    from ._lib import stream_handle
+    if not (isinstance(weights, torch.Tensor) and weights.is_cuda
+            and weights.dtype == torch.float32 and weights.numel() == col.numel()):
+        raise TypeError("weights must be a CUDA float32 tensor shaped like col")
+    V = rowptr.numel() - 1
+    row = torch.repeat_interleave(torch.arange(V, device=col.device, dtype=torch.int64),
+                                  rowptr[1:] - rowptr[:-1])
+    key, order = torch.sort((row << 32) | col.to(torch.int64), stable=True)
+    cs = (key & 0xFFFFFFFF).to(torch.int32).contiguous()
+    w = _gather_1d(weights.reshape(-1), order)
+    wcdf = torch.zeros(col.numel(), dtype=torch.int32, device=col.device)
+    status = torch.zeros(1, dtype=torch.int32, device=col.device)
+    check(_lib.lib().come_walk_cdf(ptr(rowptr), ptr(w), V, ptr(wcdf), ptr(status),
+                                   stream_handle(col.device)), "come_walk_cdf")
+    if int(status):
+        raise ValueError("edge weights must be finite and >= 0, with a positive weight in every "
+                         "row that has entries")
+    return cs, wcdf
+
+
 def device_walks(rowptr, col, starts, path_length, alpha=0.0, seed=0, walk_offset=0,
-                 emit=None, out=None, p=1.0, q=1.0, col_sorted=None, trials_out=None):
+                 emit=None, out=None, p=1.0, q=1.0, col_sorted=None, trials_out=None,
+                 weights=None, wadj=None):
     """HIP walker (come_random_walks): one walk per entry of ``starts`` (CUDA int32 positions);
     rowptr (CUDA int64 [V+1]) / col (CUDA int32) the CSR; returns CUDA int32 [P, path_length]
     (``emit[position]`` per step if given, else positions; -1 after an early stop).
@@ -294,7 +383,10 @@ def device_walks(rowptr, col, starts, path_length, alpha=0.0, seed=0, walk_offse
     anything else runs the second-order walker come_random_walks_pq (p in [2^-8, 2^8], q in
     [2^-4, 2^4]), with ``col_sorted`` = sorted_adjacency(rowptr, col), built here when it is not
     given (pass it to walk one graph repeatedly), and ``trials_out`` (a CUDA int64 tensor of one
-    element, or None) += the rejection trials of the launch."""
+    element, or None) += the rejection trials of the launch.
+    ``weights`` (CUDA float32 aligned with col), or ``wadj`` = weighted_adjacency(rowptr, col,
+    weights) built once for repeated launches: edge-weighted walks (come_random_walks_w) for any
+    (p, q), (1, 1) included; ``col``'s row order does not matter then."""
     import torch
     from ._lib import stream_handle
     for t, nm, dt in ((rowptr, "rowptr", torch.int64), (col, "col", torch.int32),
@@ -310,6 +402,22 @@ def device_walks(rowptr, col, starts, path_length, alpha=0.0, seed=0, walk_offse
         out = torch.empty((P, int(path_length)), dtype=torch.int32, device=starts.device)
     elif out.shape != (P, int(path_length)) or out.dtype != torch.int32 or not out.is_contiguous():
         raise ValueError("out must be a contiguous int32 [P, path_length] tensor")
+    if weights is not None or wadj is not None:
+        if trials_out is not None and not (trials_out.is_cuda and trials_out.numel() == 1
+                                           and trials_out.dtype == torch.int64):
+            raise TypeError("trials_out must be a CUDA int64 tensor of one element")
+        cs, wcdf = weighted_adjacency(rowptr, col, weights) if wadj is None else wadj
+        for t, nm in ((cs, "wadj[0]"), (wcdf, "wadj[1]")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32
+                    and t.is_contiguous() and t.numel() == col.numel()):
+                raise TypeError("%s must be a contiguous CUDA int32 tensor shaped like col" % nm)
+        check(_lib.lib().come_random_walks_w(
+            ptr(rowptr), ptr(cs), ptr(wcdf), V, ptr(starts), P, int(path_length), float(alpha),
+            float(p), float(q), int(seed) & (2 ** 64 - 1), int(walk_offset),
+            None if emit is None else ptr(emit), ptr(out),
+            None if trials_out is None else ptr(trials_out), stream_handle(starts.device)),
+              "come_random_walks_w")
+        return out
     if float(p) != 1.0 or float(q) != 1.0:
         if col_sorted is None:
             col_sorted = sorted_adjacency(rowptr, col)

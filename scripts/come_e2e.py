@@ -8,7 +8,10 @@ Phases (reference file:line): walks (graph_utils.py:187-192 -> device walker), O
 (node_embeddings.py:35), O2 pre-training (context_embeddings.py:41), then per outer iteration
 O1 + O2 + GMM fit (community_embeddings.py:20-37, GPU EM) + community gradient
 (community_embeddings.py:61-78).  --p / --q: node2vec's return / in-out bias of the walks (the
-second-order device walker; the default 1, 1 is the uniform walker).  Prints one JSON line.
+second-order device walker; the default 1, 1 is the uniform walker).  --w-in / --w-out: weights
+of the intra- / inter-block edges (the default 1, 1 is the unweighted run); with other values the
+walks are edge-weighted (come_random_walks_w) and the model's counts are the node strengths, from
+which the negative table, the hot rows and the quiet rows are derived.  Prints one JSON line.
 """
 import argparse
 import json
@@ -25,12 +28,12 @@ sys.path.insert(0, ROOT)
 def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negative=5,
         window=5, walk_length=40, num_walks=5, iters=1, lr=0.025, alpha=1.0, beta=0.1,
         com_iters=5, seed=0, reg_covar=1e-5, n_init=3, deterministic=False, log=print, p=1.0,
-        q=1.0):
+        q=1.0, w_in=1.0, w_out=1.0):
     import torch
     from sklearn.metrics import normalized_mutual_info_score
     from come_amd.community_embeddings import Community2Vec
     from come_amd.context_embeddings import Context2Vec
-    from come_amd.graph import random_walks, sbm
+    from come_amd.graph import CSRGraph, random_walks, sbm
     from come_amd.model import Model
     from come_amd.node_embeddings import Node2Vec
 
@@ -44,11 +47,15 @@ def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negativ
     t0 = time.time()
     g = sbm(blocks, block_size, p_in, p_out, seed=seed)
     labels = np.arange(g.V) // block_size
+    weighted = w_in != 1.0 or w_out != 1.0
+    if weighted:  # the same adjacency, intra-block edges w_in, inter-block edges w_out
+        same = labels[g.edges[:, 0]] == labels[g.edges[:, 1]]
+        g = CSRGraph(g.V, g.edges, weights=np.where(same, w_in, w_out))
     t["graph_s"] = time.time() - t0
     np.random.seed(seed)
     t0 = time.time()
-    model = Model(g.degree_by_id(), size=dim, table_size=max(10 ** 6, 100 * g.V), k=blocks,
-                  device=dev)
+    model = Model(g.degree_by_id(weighted=weighted), size=dim,
+                  table_size=max(10 ** 6, 100 * g.V), k=blocks, device=dev)
     tick("model_s", t0)
     t0 = time.time()
     walks = random_walks(g, num_walks, walk_length, seed=seed + 1, device=dev, p=p, q=q)
@@ -87,6 +94,8 @@ def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negativ
            "timings_s": {k: round(v, 4) for k, v in t.items()}}
     if p != 1.0 or q != 1.0:
         out["walk_bias"] = {"p": p, "q": q}
+    if weighted:
+        out["edge_weights"] = {"w_in": w_in, "w_out": w_out}
     log(json.dumps(out))
     return out
 
@@ -106,10 +115,13 @@ def main():
     ap.add_argument("--n-init", type=int, default=3)
     ap.add_argument("--p", type=float, default=1.0, help="node2vec return bias of the walks")
     ap.add_argument("--q", type=float, default=1.0, help="node2vec in-out bias of the walks")
+    ap.add_argument("--w-in", type=float, default=1.0, help="weight of the intra-block edges")
+    ap.add_argument("--w-out", type=float, default=1.0, help="weight of the inter-block edges")
     args = ap.parse_args()
     run(blocks=args.blocks, block_size=args.block_size, p_in=args.p_in, p_out=args.p_out,
         dim=args.dim, negative=args.negative, window=args.window, walk_length=args.walk_length,
-        num_walks=args.num_walks, iters=args.iters, n_init=args.n_init, p=args.p, q=args.q)
+        num_walks=args.num_walks, iters=args.iters, n_init=args.n_init, p=args.p, q=args.q,
+        w_in=args.w_in, w_out=args.w_out)
 
 
 if __name__ == "__main__":
