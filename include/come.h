@@ -33,7 +33,10 @@
 extern "C" {
 #endif
 
-/* ABI 5, additive: come_walk_cdf, come_random_walks_w and their CPU twins come_cpu_walk_cdf,
+/* ABI 5, additive: come_edge_cdf, come_edge_sample, their CPU twins come_cpu_edge_cdf,
+ * come_cpu_edge_sample and the test-support entry come_cpu_edge_pick (edges sampled by weight for
+ * the O1 trainer; come_sgns_o1 is unchanged).
+ * ABI 5, additive: come_walk_cdf, come_random_walks_w and their CPU twins come_cpu_walk_cdf,
  * come_cpu_random_walks_w (edge-weighted walks; the unweighted walkers are unchanged).
  * ABI 5, additive: come_random_walks_pq and its CPU twin come_cpu_random_walks_pq (node2vec
  * (p, q) second-order walks; come_random_walks is unchanged).
@@ -481,6 +484,50 @@ int come_random_walks_w(const int64_t *rowptr, const int32_t *col, const uint32_
                         float p, float q, uint64_t seed, int64_t walk_offset, const int32_t *emit,
                         int32_t *out, uint64_t *trials_out, void *stream);
 
+/* ---- Edges sampled by weight, for first-order (O1) training on a weighted graph ----
+ * The weighted first-order objective sum_e w_e log sigma(x_u . x_v) (+ negatives) is optimised by
+ * drawing edges with probability w_e / W, with replacement, and training each draw with the plain
+ * come_sgns_o1 step (LINE's edge sampling); these two entries produce the draws.
+ *
+ * come_edge_cdf.  weights: device fp32 [E], w_i >= 0.  ecdf_out: device uint64 [E].  With wmax the
+ * largest weight:
+ *     u_i     = llrint((double)w_i / (double)wmax * 2^32)          <= 2^32   (come_walk_cdf's units)
+ *     ecdf[i] = U_i = u_0 + ... + u_i                              exact, uint64
+ * E must be in [1, 2^31), so U_E < 2^63 and the words fit a signed 64-bit tensor unchanged.  No
+ * thresholds and no second rounding: the sums themselves are stored.  Only an order-free maximum
+ * and exact integer sums enter, so come_edge_cdf and come_cpu_edge_cdf give the same words bit for
+ * bit.  The device scan is four launches (maximum, per-tile totals, scan of the totals by one
+ * workgroup, per-tile rescan); no workgroup waits on another.  Uses library scratch on `stream`.
+ * Zero mass: an edge with u_i = 0 (weight 0, or below 2^-33 wmax) repeats its predecessor's sum
+ * (0 at the head of the array) and is never drawn.
+ * status: device int32, set to 0 if the CDF was built, 1 if some weight is NaN, infinite or
+ * negative or all weights are zero; ecdf_out must not be used then (its content is unspecified).
+ * Asynchronous. */
+int come_edge_cdf(const float *weights, int64_t E, uint64_t *ecdf_out, int32_t *status,
+                  void *stream);
+
+/* S draws from come_edge_cdf's distribution.  Sample s of the call is global sample gs =
+ * sample_offset + s and depends only on (seed, gs, ecdf): a list drawn in pieces with
+ * sample_offset = the piece's first index concatenates to the list drawn at once.  gs draws one
+ * Philox-4x32-10 block r[0..3] with
+ *     counter (gs low 32 bits, gs high 32 bits, 0, 0x45444745)     key (seed low, seed high)
+ * -- the walkers' counters (t, gw low, gw high, j) carry a trial index j < 4096 in the last word,
+ * so the streams of one seed never meet -- and then
+ *     r64  = r[0] << 32 | r[1]
+ *     x    = floor(r64 * U_E / 2^64)                               in [0, U_E), U_E = ecdf[E - 1]
+ *     pick = the first i with x < ecdf[i]
+ * (a search of at most 32 iterations, indices clamped to [0, E)).  Edge i is the pick for
+ * ceil(U_i 2^64 / U_E) - ceil(U_{i-1} 2^64 / U_E) of the 2^64 values of r64 (U_{-1} = 0): u_i / U_E
+ * to within 2^-64, and |u_i / U_E - w_i / W| <= (1/2 + p_i E / 2) / U_E with p_i = w_i / W, the
+ * half-unit rounding of each u_i spread over the total.
+ *   edges: device int32 [E, 2], out: device int32 [S, 2], both 8-byte aligned; out[s] =
+ *     edges[pick] as given (no orientation draw: O1 trains both directions; rows outside [0, V)
+ *     are the trainer's business).  index_out: device int64 [S] = pick, or NULL.
+ * S == 0 is a no-op; a validation failure writes nothing.  Asynchronous. */
+int come_edge_sample(const int32_t *edges, const uint64_t *ecdf, int64_t E, int64_t S,
+                     uint64_t seed, int64_t sample_offset, int32_t *out, int64_t *index_out,
+                     void *stream);
+
 /* Host, exact: build_deepwalk_corpus_iter (graph_utils.py:187-192) with the reference's own
  * random stream.  n_streams independent CPython random.Random streams (one per walk file of
  * write_walks_to_disk :122-146); stream s writes paths_per_stream[s] passes of V walks, streams
@@ -764,6 +811,18 @@ int come_cpu_random_walks_w(const int64_t *rowptr, const int32_t *col, const uin
                             int64_t V, const int32_t *starts, int64_t P, int path_length,
                             float alpha, float p, float q, uint64_t seed, int64_t walk_offset,
                             const int32_t *emit, int32_t *out, uint64_t *trials_out, int threads);
+/* come_edge_cdf and come_edge_sample on host pointers (status_out: one host int32, written; no
+ * alignment requirement): the same arithmetic and the same draw, so ecdf, status, rows and indices
+ * are the device's bit for bit, whatever `threads`.  On status 1 ecdf_out is left untouched. */
+int come_cpu_edge_cdf(const float *weights, int64_t E, uint64_t *ecdf_out, int32_t *status_out,
+                      int threads);
+int come_cpu_edge_sample(const int32_t *edges, const uint64_t *ecdf, int64_t E, int64_t S,
+                         uint64_t seed, int64_t sample_offset, int32_t *out, int64_t *index_out,
+                         int threads);
+/* Test support: idx_out[k] = the sampler's pick for the 64-bit uniform r64[k] (the r64 above in
+ * place of a Philox draw), k < n. */
+int come_cpu_edge_pick(const uint64_t *ecdf, int64_t E, const uint64_t *r64, int64_t n,
+                       int64_t *idx_out);
 
 /* ---- Host helpers ---- */
 

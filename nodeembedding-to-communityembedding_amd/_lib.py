@@ -40,7 +40,8 @@ SYMBOLS = ("come_abi_version", "come_last_error", "come_init", "come_exp_table",
            "come_gmm_diag_scatter", "come_community_grad_diag", "come_community_loss_diag",
            "come_quiet_rows", "come_sgns_o2_quiet", "come_random_walks_pq",
            "come_cpu_random_walks_pq", "come_walk_cdf", "come_cpu_walk_cdf",
-           "come_random_walks_w", "come_cpu_random_walks_w")
+           "come_random_walks_w", "come_cpu_random_walks_w", "come_edge_cdf",
+           "come_cpu_edge_cdf", "come_edge_sample", "come_cpu_edge_sample", "come_cpu_edge_pick")
 
 OPTION_FIELDS = ("o2_kernel", "o2_blocks_per_cu", "o2_waves_per_block",
                  "o2_static", "rows_per_wave", "o1_rows_per_wave",
@@ -169,6 +170,11 @@ def lib():
                                       P]
     L.come_cpu_random_walks_w.argtypes = [P, P, P, i64, P, i64, i32, f32, f32, f32, u64, i64, P,
                                           P, P, i32]
+    L.come_edge_cdf.argtypes = [P, i64, P, P, P]
+    L.come_cpu_edge_cdf.argtypes = [P, i64, P, P, i32]
+    L.come_edge_sample.argtypes = [P, P, i64, i64, u64, i64, P, P, P]
+    L.come_cpu_edge_sample.argtypes = [P, P, i64, i64, u64, i64, P, P, i32]
+    L.come_cpu_edge_pick.argtypes = [P, i64, P, i64, P]
     L.come_walks_reference.argtypes = [P, P, i64, i32, P, P, i32, f64, P, i32, P]
     L.come_pyrandom_seed.argtypes = [u64, P]
     L.come_pyrandom_draw.argtypes = [P, i32, u64, i64, P]

@@ -13,6 +13,8 @@ to them.
     random_walks_pq(rowptr, col, starts, path_length, alpha, p, q, seed, ...) -> walks[, trials]
     walk_cdf(rowptr, weights)                                      -> wcdf (edge-weighted walks)
     random_walks_w(rowptr, col, wcdf, starts, path_length, alpha, p, q, seed, ...) -> walks[, trials]
+    edge_cdf(weights)                                              -> ecdf (edges sampled by weight)
+    sample_edges(edges, ecdf, S, seed, offset)                     -> rows[, indices]
 
 Tables are updated in place (float32, C-contiguous, as the reference's numpy arrays).  ``mode``:
 MODE_HOGWILD = ``threads`` workers taking jobs of 150 walks / edges with lock-free updates, as the
@@ -298,3 +300,50 @@ def random_walks_w(rowptr, col, wcdf, starts, path_length, alpha=0.0, p=1.0, q=1
         None if emit is None else ptr(emit), ptr(out), ctypes.byref(trials), _threads(threads)),
         "come_cpu_random_walks_w")
     return (out, trials.value) if return_trials else out
+
+
+def edge_cdf(weights, threads=None, return_status=False):
+    """come_cpu_edge_cdf: the exact uint64 prefix sums of the weights' 2^-32 units (fp32 [E], one
+    weight per edge), come_edge_cdf's bit for bit.  Raises ValueError when the weights cannot be
+    used (NaN, infinite, negative, or all zero); with ``return_status`` returns ``(ecdf, status)``
+    instead of raising."""
+    _arr(weights, np.float32, "weights")
+    assert weights.ndim == 1
+    ecdf = np.zeros(len(weights), np.uint64)
+    status = ctypes.c_int32(0)
+    check(_lib.lib().come_cpu_edge_cdf(ptr(weights), len(weights), ptr(ecdf),
+                                       ctypes.byref(status), _threads(threads)),
+          "come_cpu_edge_cdf")
+    if return_status:
+        return ecdf, status.value
+    if status.value:
+        raise ValueError("edge weights must be finite and >= 0, with at least one positive")
+    return ecdf
+
+
+def sample_edges(edges, ecdf, S, seed, offset=0, return_index=False, threads=None):
+    """come_cpu_edge_sample: ``S`` rows of ``edges`` (int32 [E, 2]) drawn with replacement by
+    ``ecdf`` = edge_cdf(weights), the device sampler's (training_sdg_inner.sample_edges) bit for
+    bit; sample s is global sample ``offset + s`` of the stream ``seed``.  Returns int32 [S, 2],
+    or ``(rows, indices)`` with the int64 [S] positions in ``edges`` when ``return_index``."""
+    _arr(edges, np.int32, "edges")
+    _arr(ecdf, np.uint64, "ecdf")
+    assert edges.ndim == 2 and edges.shape[1] == 2 and ecdf.shape == (edges.shape[0],)
+    S = int(S)
+    out = np.empty((S, 2), np.int32)
+    index = np.empty(S, np.int64) if return_index else None
+    check(_lib.lib().come_cpu_edge_sample(
+        ptr(edges), ptr(ecdf), len(ecdf), S, int(seed) & (2 ** 64 - 1), int(offset), ptr(out),
+        ptr(index) if return_index else None, _threads(threads)), "come_cpu_edge_sample")
+    return (out, index) if return_index else out
+
+
+def edge_pick(ecdf, r64):
+    """come_cpu_edge_pick (test support): the sampler's pick for each 64-bit uniform of ``r64``
+    (uint64 [n]) in place of a Philox draw; int64 [n]."""
+    _arr(ecdf, np.uint64, "ecdf")
+    _arr(r64, np.uint64, "r64")
+    idx = np.empty(len(r64), np.int64)
+    check(_lib.lib().come_cpu_edge_pick(ptr(ecdf), len(ecdf), ptr(r64), len(r64), ptr(idx)),
+          "come_cpu_edge_pick")
+    return idx

@@ -29,6 +29,8 @@
 //                            bit for bit; walks split over the threads.
 //   come_cpu_walk_cdf / come_cpu_random_walks_w  edge-weighted walks: the same header's CDF
 //                            arithmetic and pq_step<true>, as k_walk_cdf / k_random_walks_w.
+//   come_cpu_edge_cdf / come_cpu_edge_sample / come_cpu_edge_pick  edge sampling by weight for
+//                            O1: come_edge_sample.h's CDF and draw, as k_edge_cdf / k_edge_sample.
 // Each compute body is built twice, for AVX2+FMA and for the baseline ISA (explicit fmaf either
 // way, -ffp-contract=off: identical results), and the first call picks one from the CPU.
 #include <stdint.h>
@@ -43,6 +45,7 @@
 #include <vector>
 
 #include "../../include/come.h"
+#include "come_edge_sample.h"
 #include "come_walk_pq.h"
 
 namespace come {
@@ -804,5 +807,88 @@ extern "C" int come_cpu_random_walks_w(const int64_t *rowptr, const int32_t *col
         total += trials;
     });
     if (trials_out) *trials_out += total.load();
+    return COME_OK;
+}
+
+// come_edge_cdf on host memory: cdf_units and an exact uint64 running sum.  The maximum does not
+// depend on an order and the sums are integers, so this is the device scan's ecdf bit for bit,
+// whatever its tiling.  One pass per phase; `threads` splits the maximum only (the sum is one
+// sequential pass, memory-bound).
+extern "C" int come_cpu_edge_cdf(const float *weights, int64_t E, uint64_t *ecdf_out,
+                                 int32_t *status_out, int threads) {
+    using namespace come;
+    if (E <= 0 || E > INT32_MAX)
+        return set_error(COME_E_INVALID, "cpu_edge_cdf: E must be in [1, 2^31)");
+    int rc = check_threads(threads);
+    if (rc) return rc;
+    if (!weights || !ecdf_out || !status_out)
+        return set_error(COME_E_INVALID, "cpu_edge_cdf: null pointer");
+    std::atomic<int32_t> bad(0);
+    std::atomic<uint32_t> wmax_bits(0);  // non-negative floats order as their bits
+    parallel_rows(E, threads, [&](int64_t lo, int64_t hi) {
+        float m = 0.0f;
+        bool ok = true;
+        for (int64_t i = lo; i < hi; ++i) {
+            const float x = weights[i];
+            ok = ok && cdf_weight_ok(x);
+            m = x > m ? x : m;
+        }
+        if (!ok) bad = 1;
+        uint32_t bits, seen = wmax_bits.load();
+        memcpy(&bits, &m, sizeof bits);
+        while (m > 0.0f && bits > seen && !wmax_bits.compare_exchange_weak(seen, bits)) {
+        }
+    });
+    float wmax;
+    const uint32_t bits = wmax_bits.load();
+    memcpy(&wmax, &bits, sizeof wmax);
+    if (bad.load() || !(wmax > 0.0f)) {
+        *status_out = 1;
+        return COME_OK;
+    }
+    uint64_t U = 0;
+    for (int64_t i = 0; i < E; ++i) {
+        U += cdf_units(weights[i], wmax);
+        ecdf_out[i] = U;
+    }
+    *status_out = 0;
+    return COME_OK;
+}
+
+// Test support: the sampler's pick for given 64-bit uniforms, idx_out[k] = edge_pick(r64[k]).
+extern "C" int come_cpu_edge_pick(const uint64_t *ecdf, int64_t E, const uint64_t *r64, int64_t n,
+                                  int64_t *idx_out) {
+    using namespace come;
+    if (E <= 0 || E > INT32_MAX)
+        return set_error(COME_E_INVALID, "cpu_edge_pick: E must be in [1, 2^31)");
+    if (n < 0) return set_error(COME_E_INVALID, "cpu_edge_pick: n must be >= 0");
+    if (n == 0) return COME_OK;
+    if (!ecdf || !r64 || !idx_out) return set_error(COME_E_INVALID, "cpu_edge_pick: null pointer");
+    for (int64_t k = 0; k < n; ++k) idx_out[k] = edge_pick(ecdf, E, r64[k]);
+    return COME_OK;
+}
+
+// The sampler on host memory: edge_r64 and edge_pick, the kernel's own draw.
+extern "C" int come_cpu_edge_sample(const int32_t *edges, const uint64_t *ecdf, int64_t E,
+                                    int64_t S, uint64_t seed, int64_t sample_offset, int32_t *out,
+                                    int64_t *index_out, int threads) {
+    using namespace come;
+    if (E <= 0 || E > INT32_MAX)
+        return set_error(COME_E_INVALID, "cpu_edge_sample: E must be in [1, 2^31)");
+    if (S < 0 || sample_offset < 0)
+        return set_error(COME_E_INVALID, "cpu_edge_sample: S and sample_offset must be >= 0");
+    int rc = check_threads(threads);
+    if (rc) return rc;
+    if (S == 0) return COME_OK;
+    if (!edges || !ecdf || !out) return set_error(COME_E_INVALID, "cpu_edge_sample: null pointer");
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    parallel_rows(S, threads, [&](int64_t lo, int64_t hi) {
+        for (int64_t s = lo; s < hi; ++s) {
+            const int64_t pick = edge_pick(ecdf, E, edge_r64((uint64_t)(sample_offset + s), k0, k1));
+            out[2 * s] = edges[2 * pick];
+            out[2 * s + 1] = edges[2 * pick + 1];
+            if (index_out) index_out[s] = pick;
+        }
+    });
     return COME_OK;
 }

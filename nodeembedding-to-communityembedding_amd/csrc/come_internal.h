@@ -31,7 +31,8 @@ int64_t *launch_counter(int device, void *stream);
 constexpr int kScratchGmmFlags = 0, kScratchGmmPt = 1, kScratchHotCounts = 2, kScratchHotBits = 3,
               kScratchGmmTri = 4, kScratchCommSplit = 5, kScratchRespSplit = 6,
               kScratchLossPartial = 7, kScratchSgnsLossVals = 8, kScratchSgnsLossCnt = 9,
-              kScratchSgnsLossPart = 10, kScratchDiagImage = 11, kScratchSlots = 12;
+              kScratchSgnsLossPart = 10, kScratchDiagImage = 11, kScratchEdgeWmax = 12,
+              kScratchSlots = 13;
 float *stream_scratch(int device, void *stream, int slot, size_t bytes);
 int scratch_failed();
 // The contended-row bitmap a Hogwild launch uses when the caller passes none (come_hot.hip):

@@ -21,10 +21,13 @@ class CSRGraph(object):
     """Undirected simple graph in CSR form over rows 0..V-1 (node id = row + 1).  ``weights``
     (one per edge row, optional): ``.weights`` is float32 aligned with ``.col``, the same on both
     directions of an edge, and ``.strength`` float64 [V] the sum per node; for a pair listed more
-    than once the last listing wins (nx.Graph.add_weighted_edges_from).  Without weights
-    ``.weights`` is None and ``.strength`` the degree."""
+    than once the last listing wins (nx.Graph.add_weighted_edges_from).  ``.edge_weights`` is
+    float32 [E], one weight per undirected edge, aligned with ``.edges`` and ``edge_ids()`` (what
+    Node2Vec.train(weights=) takes).  Without weights ``.weights`` and ``.edge_weights`` are None
+    and ``.strength`` the degree."""
 
     weights = None
+    edge_weights = None
 
     def __init__(self, V, edges_rows, weights=None):
         self.V = int(V)
@@ -52,6 +55,7 @@ class CSRGraph(object):
         self.rowptr = np.zeros(V + 1, np.int64)
         np.cumsum(self.degree, out=self.rowptr[1:])
         if weights is not None:
+            self.edge_weights = np.ascontiguousarray(w)
             self.weights = np.ascontiguousarray(np.concatenate([w, w])[order])
 
     @property

@@ -9,6 +9,11 @@ trains the pairs (edge[0] -> edge[1]) then (edge[1] -> edge[0]) on node_embeddin
 reference with workers=1).  ``loss`` reproduces :26-31 (-sum log sigma(u.v) over the edges;
 ``backend='native'`` evaluates it in one kernel launch).
 
+Edge weights (``train(..., weights=)``, ``loss(..., weights=)``): the weighted first-order
+objective sum_e w_e log sigma(x_u . x_v) is trained by edge sampling -- each pass draws edges with
+probability w_e / W on the device (training_sdg_inner.edge_cdf / sample_edges) and trains the
+draws with the same launch and the plain step.  Without weights nothing changes.
+
 Multi-GPU (``distributed=True``): every rank is handed the same edge list, draws
 every edge's seed per pass (the global numpy RNG advances as in one process), trains its
 contiguous shard of each pass and exchanges its node_embedding progress with the other ranks
@@ -99,27 +104,71 @@ class Node2Vec(object):
         rows[bad] = -1
         return rows.astype(np.int32)
 
-    def loss(self, model, edges, backend='torch'):
+    def loss(self, model, edges, backend='torch', weights=None):
         """-sum log sigma(x_v . x_u) over the valid edges (:26-31).  backend 'torch' (default): a
         gather-multiply-sum chain with two [E x d] temporaries; 'native': one
         training_sdg_inner.sgns_pairs_loss launch (no negatives, no temporaries; the trainer's
-        fp32 dot order, float64 softplus)."""
+        fp32 dot order, float64 softplus).  ``weights`` (one per row of ``edges``): the weighted
+        first-order objective -sum_e w_e log sigma(x_u . x_v) instead -- the per-edge terms of the
+        same launch / chain times the weights, summed in float64 on the device."""
         import torch
+        dev = model.node_embedding.device
+        if weights is not None:
+            w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+            if len(w) != len(np.asarray(edges).reshape(-1, 2)):
+                raise ValueError("weights must hold one value per row of edges")
+            w = torch.from_numpy(w).to(dev)
         if backend == 'native':
-            rows = torch.from_numpy(self._edge_rows(model, edges)).to(model.node_embedding.device)
+            rows = torch.from_numpy(self._edge_rows(model, edges)).to(dev)
             x = model.node_embedding
-            return tsi.sgns_pairs_loss(x, x, rows[:, 0].contiguous(), rows[:, 1].contiguous())[0]
+            r0, r1 = rows[:, 0].contiguous(), rows[:, 1].contiguous()
+            if weights is None:
+                return tsi.sgns_pairs_loss(x, x, r0, r1)[0]
+            per = tsi.sgns_pairs_loss(x, x, r0, r1, return_pairs=True)[2]
+            return float((per * w)[rows[:, 0] >= 0].sum())
         if backend != 'torch':
             raise ValueError("backend must be 'torch' or 'native'")
-        rows = torch.from_numpy(self._edge_rows(model, edges)).to(model.node_embedding.device)
-        rows = rows[(rows >= 0).all(dim=1)].long()
+        rows = torch.from_numpy(self._edge_rows(model, edges)).to(dev)
+        ok = (rows >= 0).all(dim=1)
+        rows = rows[ok].long()
         x = model.node_embedding
         dots = (x[rows[:, 1]] * x[rows[:, 0]]).sum(dim=1).double()
-        return float(-torch.nn.functional.logsigmoid(dots).sum())
+        if weights is None:
+            return float(-torch.nn.functional.logsigmoid(dots).sum())
+        return float(-(torch.nn.functional.logsigmoid(dots) * w[ok]).sum())
 
-    def train(self, model, edges, chunksize=150, iter=1):
+    def _weighted_cdf(self, rows, weights, dev):
+        """(ecdf, positive rows) of one pass: the weights of skipped rows (-1: an OOV or
+        down-sampled endpoint) set to 0, then training_sdg_inner.edge_cdf on the device."""
+        import torch
+        w = np.array(weights, np.float32).reshape(-1)
+        if len(w) != rows.shape[0]:
+            raise ValueError("weights must hold one value per row of edges")
+        w[rows[:, 0] < 0] = 0.0
+        return tsi.edge_cdf(torch.from_numpy(w).to(dev)), int((w > 0).sum())
+
+    def train(self, model, edges, chunksize=150, iter=1, weights=None, samples=None, seed=None):
+        """One pass over ``edges`` per ``iter``, every edge once (see the module docstring).
+
+        ``weights`` (one value >= 0 per row of ``edges``): edge sampling for the weighted
+        first-order objective sum_e w_e log sigma(x_u . x_v) + negatives.  Each pass draws
+        ``samples`` edges (default: the number of rows with positive weight) with probability
+        w_e / W, with replacement, on the device (training_sdg_inner.edge_cdf once per call --
+        once per pass with down-sampling -- then sample_edges) and trains the draws with the plain
+        step, per-sample seeds from draw_seeds exactly as a pass over ``samples`` edges.  Rows
+        with an OOV or down-sampled endpoint get weight 0.  The draws of pass k come from the
+        Philox stream ``seed + k``; ``seed=None`` takes one 64-bit value per pass from the global
+        numpy RNG (``np.random.randint(0, 2 ** 64, dtype=np.uint64)``), before that pass's
+        draw_seeds.  ``deterministic=True`` trains the same draws in order on one wavefront.
+        ``distributed=True`` needs no new exchange: every rank draws the identical sample list
+        (as every rank draws every edge's seed) and trains its contiguous shard of it.  Build the
+        model's counts from strengths (CSRGraph.degree_by_id(weighted=True)): the endpoints of
+        sampled edges appear in proportion to strength.  Without ``weights`` nothing changes, the
+        global numpy RNG's draws included.  Returns the pairs trained."""
         import torch
         assert model.node_embedding.dtype == torch.float32
+        if weights is None and (samples is not None or seed is not None):
+            raise ValueError("samples and seed belong to edge sampling: pass weights")
         start = time.time()
         rows = self._edge_rows(model, edges)
         dev = model.node_embedding.device
@@ -132,26 +181,39 @@ class Node2Vec(object):
         pairs = 0
         n_valid = None
         seeds_to = _SeedUpload(dev)
+        ecdf = None
         for it in range(int(iter)):
             if it > 0 and model.down_sampling:  # every pass draws its own sample (:47)
                 rows = self._edge_rows(model, edges)
                 ed = torch.from_numpy(rows).to(dev)
                 n_valid = None
-            lo, hi = shard_range(rows.shape[0], rank, world)
-            if n_valid is None:
+                ecdf = None
+            if weights is None:
+                batch, n = ed, rows.shape[0]
+            else:  # this pass's corpus: n draws by weight, every one a valid edge
+                if ecdf is None:
+                    ecdf, positive = self._weighted_cdf(rows, weights, dev)
+                n = positive if samples is None else int(samples)
+                s64 = (int(np.random.randint(0, 2 ** 64, dtype=np.uint64)) if seed is None
+                       else int(seed) + it)
+                batch = tsi.sample_edges(ed, ecdf, n, s64)
+            lo, hi = shard_range(n, rank, world)
+            if weights is not None:
+                n_valid = 2 * (hi - lo)
+            elif n_valid is None:
                 n_valid = 2 * int((rows[lo:hi] >= 0).all(axis=1).sum())
             pairs += n_valid
-            sd = seeds_to(rows.shape[0])
+            sd = seeds_to(n)
             if ex is None:
-                tsi.sgns_o1(model.node_embedding, ed, sd, self.negative, model.negative_table(),
-                            self.lr, mode, hot=hot)
+                tsi.sgns_o1(model.node_embedding, batch, sd, self.negative,
+                            model.negative_table(), self.lr, mode, hot=hot)
                 continue
             # every rank makes the same number of exchanges per pass (rank 0's shard is largest)
-            per = self.sync_edges or max(1, shard_range(rows.shape[0], 0, world)[1])
-            for b in range(max(1, -(-shard_range(rows.shape[0], 0, world)[1] // per))):
+            per = self.sync_edges or max(1, shard_range(n, 0, world)[1])
+            for b in range(max(1, -(-shard_range(n, 0, world)[1] // per))):
                 s, e = min(hi, lo + b * per), min(hi, lo + (b + 1) * per)
                 if e > s:
-                    tsi.sgns_o1(model.node_embedding, ed[s:e], sd[s:e], self.negative,
+                    tsi.sgns_o1(model.node_embedding, batch[s:e], sd[s:e], self.negative,
                                 model.negative_table(), self.lr, mode, hot=hot)
                 ex.sync()
         if model.node_embedding.is_cuda:

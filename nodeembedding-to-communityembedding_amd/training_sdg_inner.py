@@ -271,6 +271,45 @@ def sgns_o1(node, edges, seeds, negative, table, lr, mode=MODE_HOGWILD, opts=Non
     check(rc, "come_sgns_o1")
 
 
+def edge_cdf(weights):
+    """come_edge_cdf: the sampler's CDF of per-edge ``weights`` (CUDA float32 [E], >= 0) -- a CUDA
+    int64 tensor [E] holding the exact uint64 prefix sums of the weights in units of 2^-32 of the
+    largest (below 2^63, so the bits are the same).  Once per graph.  ValueError when the weights
+    cannot be used (NaN, infinite, negative, or all zero)."""
+    import torch
+    _require_cuda(weights, "weights", torch.float32)
+    if weights.dim() != 1 or weights.numel() < 1:
+        raise ValueError("weights must be [E] with E >= 1")
+    ecdf = torch.zeros(weights.numel(), dtype=torch.int64, device=weights.device)
+    status = torch.zeros(1, dtype=torch.int32, device=weights.device)
+    check(_lib.lib().come_edge_cdf(ptr(weights), weights.numel(), ptr(ecdf), ptr(status),
+                                   stream_handle(weights.device)), "come_edge_cdf")
+    if int(status.item()):
+        raise ValueError("edge weights must be finite and >= 0, with at least one positive")
+    return ecdf
+
+
+def sample_edges(edges, ecdf, S, seed, offset=0, return_index=False):
+    """come_edge_sample: ``S`` rows of ``edges`` (CUDA int32 [E, 2]) drawn with replacement with
+    probability w_e / W, ``ecdf`` = edge_cdf(weights).  Sample s is global sample ``offset + s``
+    of the Philox stream ``seed``: pieces drawn at consecutive offsets concatenate to the list
+    drawn at once.  Returns CUDA int32 [S, 2] (what sgns_o1 takes), or ``(rows, indices)`` with the
+    CUDA int64 [S] positions in ``edges`` when ``return_index``."""
+    import torch
+    _require_cuda(edges, "edges", torch.int32)
+    _require_cuda(ecdf, "ecdf", torch.int64)
+    if edges.dim() != 2 or edges.shape[1] != 2 or ecdf.shape != (edges.shape[0],):
+        raise ValueError("edges must be [E, 2] and ecdf [E]")
+    S = int(S)
+    out = torch.empty((S, 2), dtype=torch.int32, device=edges.device)
+    index = torch.empty(S, dtype=torch.int64, device=edges.device) if return_index else None
+    check(_lib.lib().come_edge_sample(ptr(edges), ptr(ecdf), edges.shape[0], S,
+                                      int(seed) & (2 ** 64 - 1), int(offset), ptr(out),
+                                      ptr(index) if return_index else None,
+                                      stream_handle(edges.device)), "come_edge_sample")
+    return (out, index) if return_index else out
+
+
 def sgns_o2_loss(node, ctx, walks, seeds, window, negative, table, return_walks=False):
     """The SGNS objective of exactly the batch ``sgns_o2`` would train on with these ``walks`` [P, L]
     and ``seeds`` [P] (come_sgns_o2_loss: same pairs, same LCG negatives, the trainer's fp32 dot,

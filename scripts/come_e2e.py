@@ -11,7 +11,9 @@ O1 + O2 + GMM fit (community_embeddings.py:20-37, GPU EM) + community gradient
 second-order device walker; the default 1, 1 is the uniform walker).  --w-in / --w-out: weights
 of the intra- / inter-block edges (the default 1, 1 is the unweighted run); with other values the
 walks are edge-weighted (come_random_walks_w) and the model's counts are the node strengths, from
-which the negative table, the hot rows and the quiet rows are derived.  Prints one JSON line.
+which the negative table, the hot rows and the quiet rows are derived.  --weighted-o1 (off by
+default; needs --w-in or --w-out): the O1 passes train edges sampled by weight on the device
+(Node2Vec.train(weights=g.edge_weights)) instead of every edge once.  Prints one JSON line.
 """
 import argparse
 import json
@@ -28,7 +30,7 @@ sys.path.insert(0, ROOT)
 def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negative=5,
         window=5, walk_length=40, num_walks=5, iters=1, lr=0.025, alpha=1.0, beta=0.1,
         com_iters=5, seed=0, reg_covar=1e-5, n_init=3, deterministic=False, log=print, p=1.0,
-        q=1.0, w_in=1.0, w_out=1.0):
+        q=1.0, w_in=1.0, w_out=1.0, weighted_o1=False):
     import torch
     from sklearn.metrics import normalized_mutual_info_score
     from come_amd.community_embeddings import Community2Vec
@@ -48,6 +50,8 @@ def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negativ
     g = sbm(blocks, block_size, p_in, p_out, seed=seed)
     labels = np.arange(g.V) // block_size
     weighted = w_in != 1.0 or w_out != 1.0
+    if weighted_o1 and not weighted:
+        raise ValueError("--weighted-o1 needs edge weights: pass --w-in or --w-out")
     if weighted:  # the same adjacency, intra-block edges w_in, inter-block edges w_out
         same = labels[g.edges[:, 0]] == labels[g.edges[:, 1]]
         g = CSRGraph(g.V, g.edges, weights=np.where(same, w_in, w_out))
@@ -62,20 +66,21 @@ def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negativ
     walks_ids = torch.where(walks >= 0, walks + 1, walks)  # rows -> node ids (ids = row + 1)
     tick("walks_s", t0)
     edges = g.edge_ids()
+    o1w = {"weights": g.edge_weights} if weighted_o1 else {}  # sampler seeds: the numpy RNG
     nl = Node2Vec(lr=lr, negative=negative, deterministic=deterministic)
     cl = Context2Vec(lr=lr, window_size=window, negative=negative, deterministic=deterministic)
     cm = Community2Vec(model, lr=lr, reg_covar=reg_covar)
     cm.g_mixture.n_init = n_init
     pairs = 0
     t0 = time.time()
-    nl.train(model, edges=edges, iter=1)
+    nl.train(model, edges=edges, iter=1, **o1w)
     tick("o1_s", t0)
     t0 = time.time()
     pairs += cl.train(model, paths=walks_ids, total_nodes=walks.numel(), alpha=alpha)
     tick("o2_s", t0)
     for _ in range(iters):
         t0 = time.time()
-        nl.train(model, edges=edges, iter=1)
+        nl.train(model, edges=edges, iter=1, **o1w)
         tick("o1_s", t0)
         t0 = time.time()
         pairs += cl.train(model, paths=walks_ids, total_nodes=walks.numel(), alpha=alpha)
@@ -95,7 +100,7 @@ def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negativ
     if p != 1.0 or q != 1.0:
         out["walk_bias"] = {"p": p, "q": q}
     if weighted:
-        out["edge_weights"] = {"w_in": w_in, "w_out": w_out}
+        out["edge_weights"] = {"w_in": w_in, "w_out": w_out, "weighted_o1": bool(weighted_o1)}
     log(json.dumps(out))
     return out
 
@@ -117,11 +122,13 @@ def main():
     ap.add_argument("--q", type=float, default=1.0, help="node2vec in-out bias of the walks")
     ap.add_argument("--w-in", type=float, default=1.0, help="weight of the intra-block edges")
     ap.add_argument("--w-out", type=float, default=1.0, help="weight of the inter-block edges")
+    ap.add_argument("--weighted-o1", action="store_true",
+                    help="train O1 on edges sampled by weight (needs --w-in or --w-out)")
     args = ap.parse_args()
     run(blocks=args.blocks, block_size=args.block_size, p_in=args.p_in, p_out=args.p_out,
         dim=args.dim, negative=args.negative, window=args.window, walk_length=args.walk_length,
         num_walks=args.num_walks, iters=args.iters, n_init=args.n_init, p=args.p, q=args.q,
-        w_in=args.w_in, w_out=args.w_out)
+        w_in=args.w_in, w_out=args.w_out, weighted_o1=args.weighted_o1)
 
 
 if __name__ == "__main__":
