@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* ABI 5, additive: come_edge_cdf, come_edge_sample, their CPU twins come_cpu_edge_cdf,
+/* ABI 5 (no signature or struct changed): the launch option "walk_staged" accepts 0 / 1 only; the
+ * A/B values 2 / 3 (8- and 32-step slices of the same walks) are COME_E_INVALID at come_random_walks.
+ * ABI 5, additive: come_edge_cdf, come_edge_sample, their CPU twins come_cpu_edge_cdf,
  * come_cpu_edge_sample and the test-support entry come_cpu_edge_pick (edges sampled by weight for
  * the O1 trainer; come_sgns_o1 is unchanged).
  * ABI 5, additive: come_walk_cdf, come_random_walks_w and their CPU twins come_cpu_walk_cdf,
@@ -632,8 +634,8 @@ int come_delta_scatter(float *W, float *S, const int64_t *idx, int64_t n, int d,
  *                       staging wavefronts); 5 = k_gmm_cov_bf3 at both widths (5.5 ms at C4);
  *                       3 = k_gmm_cov16 (fp32 16x16x4 tiles: 36 of 64 upper tiles at d = 128;
  *                       7.22 ms).  Other values: COME_E_INVALID
- *   walk_staged         default 1: LDS-staged walker output (2 = 8-step, 3 = 32-step slices);
- *                       0 = one store per lane per step (identical walks)
+ *   walk_staged         come_random_walks: default 1 = LDS-staged walker output; 0 = one store per
+ *                       lane per step (identical walks).  Other values: COME_E_INVALID
  *   o2_fresh_loads      direct kernel: rows read with agent-scope loads (bypass the CU's L1)
  *   o2_atomic_writeback direct kernel: every row update written as a float-atomic delta
  *   gmm_resp16          GMM E-step at d = 64, 128: default 3 = k_gmm_resp_b16 (fp32 operands

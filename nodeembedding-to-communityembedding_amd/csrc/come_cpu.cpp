@@ -673,35 +673,14 @@ extern "C" int come_cpu_sgns_pairs_loss(const float *inp, const float *out, int6
     return COME_OK;
 }
 
-// The (p, q) walker on host memory: come_walk_pq.h's pq_step, the kernel's own step body, walk by
-// walk.  A walk depends only on its global index, so the split over threads changes nothing.
-extern "C" int come_cpu_random_walks_pq(const int64_t *rowptr, const int32_t *col,
-                                        const int32_t *col_sorted, int64_t V,
-                                        const int32_t *starts, int64_t P, int L, float alpha,
-                                        float p, float q, uint64_t seed, int64_t walk_offset,
-                                        const int32_t *emit, int32_t *out, uint64_t *trials_out,
-                                        int threads) {
+// The (p, q) and weighted walkers on host memory: come_walk_pq.h's pq_step<W>, the kernels' own
+// step body, walk by walk.  A walk depends only on its global index, so the split over threads
+// changes nothing.
+template <bool W>
+static void cpu_walks(const come::PqGraph &g, const come::PqParams &pp, int64_t V,
+                      const int32_t *starts, int64_t P, int L, uint64_t seed, int64_t walk_offset,
+                      const int32_t *emit, int32_t *out, uint64_t *trials_out, int threads) {
     using namespace come;
-    if (V <= 0 || V > INT32_MAX)
-        return set_error(COME_E_INVALID, "cpu_random_walks_pq: V must be in [1, 2^31)");
-    if (P < 0 || L < 0 || walk_offset < 0)
-        return set_error(COME_E_INVALID,
-                         "cpu_random_walks_pq: P, L and walk_offset must be >= 0");
-    if (!(alpha >= 0.0f && alpha <= 1.0f))
-        return set_error(COME_E_INVALID, "cpu_random_walks_pq: alpha not in [0,1]");
-    if (!pq_in_range(p, q))
-        return set_error(COME_E_INVALID,
-                         "cpu_random_walks_pq: p must be in [2^-8, 2^8] and q in [2^-4, 2^4]");
-    int rc = check_threads(threads);
-    if (rc) return rc;
-    if (P == 0 || L == 0) return COME_OK;
-    if (!rowptr || !col || !starts || !out)
-        return set_error(COME_E_INVALID, "cpu_random_walks_pq: null pointer");
-    if (!col_sorted && pq_needs_sorted(p, q))
-        return set_error(COME_E_INVALID,
-                         "cpu_random_walks_pq: col_sorted may be NULL only with q == 1 and p >= 1");
-    const PqGraph g{rowptr, col, col_sorted, rowptr[V], nullptr};
-    const PqParams pp = pq_make_params(alpha, p, q);
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     std::atomic<uint64_t> total(0);
     parallel_rows(P, threads, [&](int64_t lo, int64_t hi) {
@@ -713,13 +692,34 @@ extern "C" int come_cpu_random_walks_pq(const int64_t *rowptr, const int32_t *co
             bool alive = start >= 0 && start < V;  // not a node: an empty walk
             PqWalk s{alive ? start : -1, -1, 0, 0};
             for (int t = 0; t < L; ++t) {
-                if (alive && t > 0) trials += pq_step(g, pp, start, (uint32_t)t, gw, k0, k1, s, alive);
+                if (alive && t > 0)
+                    trials += pq_step<W>(g, pp, start, (uint32_t)t, gw, k0, k1, s, alive);
                 row[t] = alive ? (emit ? emit[s.cur] : s.cur) : -1;
             }
         }
         total += trials;
     });
     if (trials_out) *trials_out += total.load();
+}
+
+extern "C" int come_cpu_random_walks_pq(const int64_t *rowptr, const int32_t *col,
+                                        const int32_t *col_sorted, int64_t V,
+                                        const int32_t *starts, int64_t P, int L, float alpha,
+                                        float p, float q, uint64_t seed, int64_t walk_offset,
+                                        const int32_t *emit, int32_t *out, uint64_t *trials_out,
+                                        int threads) {
+    using namespace come;
+    bool run;
+    int rc = walk_check_args("cpu_random_walks_pq: ", V, P, L, walk_offset, alpha, p, q,
+                             rowptr && col && starts && out, &run,
+                             [&] { return check_threads(threads); });
+    if (rc || !run) return rc;
+    if (!col_sorted && pq_needs_sorted(p, q))
+        return set_error(COME_E_INVALID,
+                         "cpu_random_walks_pq: col_sorted may be NULL only with q == 1 and p >= 1");
+    cpu_walks<false>(PqGraph{rowptr, col, col_sorted, rowptr[V], nullptr},
+                     pq_make_params(alpha, p, q), V, starts, P, L, seed, walk_offset, emit, out,
+                     trials_out, threads);
     return COME_OK;
 }
 
@@ -765,48 +765,19 @@ extern "C" int come_cpu_walk_cdf(const int64_t *rowptr, const float *weights, in
     return COME_OK;
 }
 
-// The weighted walker on host memory: pq_step<true>, the kernel's own step body.
 extern "C" int come_cpu_random_walks_w(const int64_t *rowptr, const int32_t *col,
                                        const uint32_t *wcdf, int64_t V, const int32_t *starts,
                                        int64_t P, int L, float alpha, float p, float q,
                                        uint64_t seed, int64_t walk_offset, const int32_t *emit,
                                        int32_t *out, uint64_t *trials_out, int threads) {
     using namespace come;
-    if (V <= 0 || V > INT32_MAX)
-        return set_error(COME_E_INVALID, "cpu_random_walks_w: V must be in [1, 2^31)");
-    if (P < 0 || L < 0 || walk_offset < 0)
-        return set_error(COME_E_INVALID, "cpu_random_walks_w: P, L and walk_offset must be >= 0");
-    if (!(alpha >= 0.0f && alpha <= 1.0f))
-        return set_error(COME_E_INVALID, "cpu_random_walks_w: alpha not in [0,1]");
-    if (!pq_in_range(p, q))
-        return set_error(COME_E_INVALID,
-                         "cpu_random_walks_w: p must be in [2^-8, 2^8] and q in [2^-4, 2^4]");
-    int rc = check_threads(threads);
-    if (rc) return rc;
-    if (P == 0 || L == 0) return COME_OK;
-    if (!rowptr || !col || !wcdf || !starts || !out)
-        return set_error(COME_E_INVALID, "cpu_random_walks_w: null pointer");
-    const PqGraph g{rowptr, col, col, rowptr[V], wcdf};
-    const PqParams pp = pq_make_params(alpha, p, q);
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    std::atomic<uint64_t> total(0);
-    parallel_rows(P, threads, [&](int64_t lo, int64_t hi) {
-        uint64_t trials = 0;
-        for (int64_t w = lo; w < hi; ++w) {
-            int32_t *row = out + w * (int64_t)L;
-            const int32_t start = starts[w];
-            const uint64_t gw = (uint64_t)(walk_offset + w);
-            bool alive = start >= 0 && start < V;  // not a node: an empty walk
-            PqWalk s{alive ? start : -1, -1, 0, 0};
-            for (int t = 0; t < L; ++t) {
-                if (alive && t > 0)
-                    trials += pq_step<true>(g, pp, start, (uint32_t)t, gw, k0, k1, s, alive);
-                row[t] = alive ? (emit ? emit[s.cur] : s.cur) : -1;
-            }
-        }
-        total += trials;
-    });
-    if (trials_out) *trials_out += total.load();
+    bool run;
+    int rc = walk_check_args("cpu_random_walks_w: ", V, P, L, walk_offset, alpha, p, q,
+                             rowptr && col && wcdf && starts && out, &run,
+                             [&] { return check_threads(threads); });
+    if (rc || !run) return rc;
+    cpu_walks<true>(PqGraph{rowptr, col, col, rowptr[V], wcdf}, pq_make_params(alpha, p, q), V,
+                    starts, P, L, seed, walk_offset, emit, out, trials_out, threads);
     return COME_OK;
 }
 

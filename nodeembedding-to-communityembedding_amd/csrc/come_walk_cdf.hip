@@ -1,9 +1,8 @@
-// come_walk_w.hip -- edge-weighted random walks on the device (gfx950): the per-row CDF build
-// (k_walk_cdf) and the weighted (p, q) walker (k_random_walks_w).
+// come_walk_cdf.hip -- the per-row CDF build of the edge-weighted walks (gfx950): k_walk_cdf.  The
+// walker that reads it is k_random_walks_w (come_walk.hip).
 //
-// The step is come_walk_pq.h's pq_step<true> and the CDF's arithmetic is cdf_units / cdf_threshold
-// of the same header, both shared with the CPU twins (come_cpu.cpp), so thresholds, walks and trial
-// counts are the host's bit for bit.
+// The CDF's arithmetic is cdf_units / cdf_threshold of come_walk_pq.h, shared with the CPU twin
+// (come_cpu.cpp), so the thresholds are the host's bit for bit.
 //
 // k_walk_cdf.  Per row: the largest weight, u_i = llrint(w_i / wmax * 2^32), the exact uint64
 // prefix sums U_i, and T_i = ceil(U_i / U_last * 2^32).  Only the maximum (order-free) and integer
@@ -12,10 +11,6 @@
 // longer rows of a wavefront's 64 are then taken one after another by the whole wavefront (a
 // shuffle scan per 64 entries, the carry in a register).  Three passes over the row (maximum,
 // total, thresholds); a one-off pass per graph.
-//
-// k_random_walks_w is k_random_walks_pq's launch: one lane per walk, 256-lane workgroups, the
-// output staged through LDS in 16-step slices.  Per trial a lane additionally walks about
-// log2(deg) dependent wcdf entries for its candidate.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -120,68 +115,6 @@ __global__ void __launch_bounds__(CDF_BLOCK) k_walk_cdf(const int64_t *__restric
     if (!ok) *status = 1;  // a plain (vector) store: every writer writes the same word
 }
 
-struct WalkWArgs {
-    const int64_t *rowptr;
-    const int32_t *col;
-    const uint32_t *wcdf;
-    const int32_t *starts;
-    const int32_t *emit;
-    int32_t *out;
-    unsigned long long *trials_out;  // += the Philox blocks this launch drew, or NULL
-    int64_t V;
-    int64_t P;
-    int64_t walk_offset;
-    uint64_t seed;
-    int L;
-    PqParams pp;
-};
-
-constexpr int WALK_W_BLOCK = 256;
-constexpr int WALK_W_CHUNK = 16;
-
-__global__ void __launch_bounds__(WALK_W_BLOCK) k_random_walks_w(WalkWArgs a) {
-    // +1: column writes hit distinct banks
-    __shared__ alignas(8) int32_t tile[WALK_W_BLOCK][WALK_W_CHUNK + 1];
-    const int tid = threadIdx.x;
-    const int64_t w0 = (int64_t)blockIdx.x * WALK_W_BLOCK;
-    const int64_t w = w0 + tid;
-    const uint64_t gw = (uint64_t)(a.walk_offset + w);
-    const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
-    const PqGraph g{a.rowptr, a.col, a.col, a.rowptr[a.V], a.wcdf};
-    int32_t start = -1;
-    if (w < a.P) start = a.starts[w];
-    bool alive = start >= 0 && start < a.V;  // not a node: an empty walk
-    PqWalk s{alive ? start : -1, -1, 0, 0};
-    uint64_t trials = 0;
-    const int64_t rows = a.P - w0 < WALK_W_BLOCK ? a.P - w0 : WALK_W_BLOCK;
-    // dead lanes and lanes past P keep going through the chunk loop (they emit -1), so every
-    // lane reaches the barriers
-    for (int c0 = 0; c0 < a.L; c0 += WALK_W_CHUNK) {
-        const int cn = a.L - c0 < WALK_W_CHUNK ? a.L - c0 : WALK_W_CHUNK;
-        for (int j = 0; j < cn; ++j) {
-            const int t = c0 + j;
-            if (alive && t > 0)
-                trials += pq_step<true>(g, a.pp, start, (uint32_t)t, gw, k0, k1, s, alive);
-            tile[tid][j] = alive ? (a.emit ? a.emit[s.cur] : s.cur) : -1;
-        }
-        __syncthreads();
-        // rows x cn slice -> global, consecutive lanes on consecutive columns of one row
-        for (int i = tid; i < (int)rows * cn; i += WALK_W_BLOCK) {
-            const int r = i / cn, j = i - r * cn;
-            a.out[(w0 + r) * (int64_t)a.L + c0 + j] = tile[r][j];
-        }
-        __syncthreads();
-    }
-    if (a.trials_out) {  // uniform: one LDS add per walk (the tile is free now), one global add
-        unsigned long long *block_trials = (unsigned long long *)&tile[0][0];
-        if (tid == 0) *block_trials = 0;
-        __syncthreads();
-        if (trials) atomicAdd(block_trials, (unsigned long long)trials);
-        __syncthreads();
-        if (tid == 0 && *block_trials) atomicAdd(a.trials_out, *block_trials);
-    }
-}
-
 }  // namespace come
 
 using namespace come;
@@ -200,31 +133,4 @@ extern "C" int come_walk_cdf(const int64_t *rowptr, const float *weights, int64_
     hipLaunchKernelGGL(k_walk_cdf, dim3((unsigned)blocks), dim3(CDF_BLOCK), 0,
                        (hipStream_t)stream, rowptr, weights, V, wcdf_out, status);
     return hip_error(hipGetLastError(), "k_walk_cdf launch");
-}
-
-extern "C" int come_random_walks_w(const int64_t *rowptr, const int32_t *col,
-                                   const uint32_t *wcdf, int64_t V, const int32_t *starts,
-                                   int64_t P, int L, float alpha, float p, float q, uint64_t seed,
-                                   int64_t walk_offset, const int32_t *emit, int32_t *out,
-                                   uint64_t *trials_out, void *stream) {
-    if (V <= 0 || V > INT32_MAX) return set_error(COME_E_INVALID, "V must be in [1, 2^31)");
-    if (P < 0 || L < 0 || walk_offset < 0)
-        return set_error(COME_E_INVALID, "P, L and walk_offset must be >= 0");
-    if (!(alpha >= 0.0f && alpha <= 1.0f)) return set_error(COME_E_INVALID, "alpha not in [0,1]");
-    if (!pq_in_range(p, q))
-        return set_error(COME_E_INVALID, "p must be in [2^-8, 2^8] and q in [2^-4, 2^4]");
-    if (P == 0 || L == 0) return COME_OK;
-    if (!rowptr || !col || !wcdf || !starts || !out)
-        return set_error(COME_E_INVALID, "null pointer");
-    int dev = 0;
-    int rc = ensure_init(&dev);
-    if (rc) return rc;
-    WalkWArgs a{rowptr, col, wcdf, starts, emit, out, (unsigned long long *)trials_out,
-                V, P, walk_offset, seed, L, pq_make_params(alpha, p, q)};
-    const int64_t blocks = (P + WALK_W_BLOCK - 1) / WALK_W_BLOCK;
-    if (blocks > INT32_MAX) return set_error(COME_E_INVALID, "too many walks in one launch");
-    void *kargs[] = {&a};
-    hipError_t e = hipLaunchKernel((const void *)k_random_walks_w, dim3((unsigned)blocks),
-                                   dim3(WALK_W_BLOCK), kargs, 0, (hipStream_t)stream);
-    return hip_error(e, "k_random_walks_w launch");
 }

@@ -1,7 +1,7 @@
 // come_walk_pq.h -- the walkers' random stream (Philox-4x32-10) and the node2vec (p, q)
-// second-order step: one copy, compiled as device code by come_walk.hip / come_walk_pq.hip /
-// come_walk_w.hip and as plain host C++ by come_cpu.cpp (the CPU twins), so the two are the same
-// walks bit for bit.
+// second-order step: one copy, compiled as device code by come_walk.hip (the walkers) and
+// come_walk_cdf.hip (the CDF build) and as plain host C++ by come_cpu.cpp (the CPU twins), so the
+// two are the same walks bit for bit.  Also the one check of the walkers' common arguments.
 //
 // Semantics.  A walk is c_0 = start.  Its first step, and the first step after a restart, is
 // uniform over N(c_0): the first-order walker's step (come_walk.hip), same Philox block, same
@@ -89,6 +89,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/come.h"
+
 #if defined(__HIPCC__)
 #define COME_HD __host__ __device__
 #else
@@ -96,6 +98,8 @@
 #endif
 
 namespace come {
+
+int set_error(int code, const char *fmt, ...);  // returns code (come_host.cpp)
 
 struct Philox {
     uint32_t r[4];
@@ -169,6 +173,38 @@ inline PqParams pq_make_params(float alpha, float p, float q) {
     pp.e = wr > M ? (uint64_t)floor((wr - M) / M * 4294967296.0 + 0.5) : 0u;
     pp.restart_threshold = walk_restart_threshold(alpha);
     return pp;
+}
+
+// The arguments every walker entry point takes, device or host, checked in the one order they
+// all report them in.  `prefix` starts each message ("" for the device entries).  The first-order
+// entry passes p = q = 1.  `pointers`: the entry's required pointers are all non-null -- looked at
+// only when there is work, *run: P == 0 or L == 0 is COME_OK with nothing to do whatever the
+// pointers are.  `also`: a check of the caller's own between the ranges and that early return (the
+// CPU twins' `threads`).
+template <class Also>
+inline int walk_check_args(const char *prefix, int64_t V, int64_t P, int L, int64_t walk_offset,
+                           float alpha, float p, float q, bool pointers, bool *run, Also also) {
+    *run = false;
+    if (V <= 0 || V > INT32_MAX)
+        return set_error(COME_E_INVALID, "%sV must be in [1, 2^31)", prefix);
+    if (P < 0 || L < 0 || walk_offset < 0)
+        return set_error(COME_E_INVALID, "%sP, L and walk_offset must be >= 0", prefix);
+    if (!(alpha >= 0.0f && alpha <= 1.0f))
+        return set_error(COME_E_INVALID, "%salpha not in [0,1]", prefix);
+    if (!pq_in_range(p, q))
+        return set_error(COME_E_INVALID, "%sp must be in [2^-8, 2^8] and q in [2^-4, 2^4]", prefix);
+    const int rc = also();
+    if (rc) return rc;
+    if (P == 0 || L == 0) return COME_OK;
+    if (!pointers) return set_error(COME_E_INVALID, "%snull pointer", prefix);
+    *run = true;
+    return COME_OK;
+}
+
+inline int walk_check_args(const char *prefix, int64_t V, int64_t P, int L, int64_t walk_offset,
+                           float alpha, float p, float q, bool pointers, bool *run) {
+    return walk_check_args(prefix, V, P, L, walk_offset, alpha, p, q, pointers, run,
+                           [] { return (int)COME_OK; });
 }
 
 struct PqGraph {

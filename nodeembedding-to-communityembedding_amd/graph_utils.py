@@ -402,15 +402,22 @@ def device_walks(rowptr, col, starts, path_length, alpha=0.0, seed=0, walk_offse
         out = torch.empty((P, int(path_length)), dtype=torch.int32, device=starts.device)
     elif out.shape != (P, int(path_length)) or out.dtype != torch.int32 or not out.is_contiguous():
         raise ValueError("out must be a contiguous int32 [P, path_length] tensor")
-    if weights is not None or wadj is not None:
+
+    def like_col(t, nm):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32
+                and t.is_contiguous() and t.numel() == col.numel()):
+            raise TypeError("%s must be a contiguous CUDA int32 tensor shaped like col" % nm)
+
+    def check_trials_out():
         if trials_out is not None and not (trials_out.is_cuda and trials_out.numel() == 1
                                            and trials_out.dtype == torch.int64):
             raise TypeError("trials_out must be a CUDA int64 tensor of one element")
+
+    if weights is not None or wadj is not None:
+        check_trials_out()
         cs, wcdf = weighted_adjacency(rowptr, col, weights) if wadj is None else wadj
-        for t, nm in ((cs, "wadj[0]"), (wcdf, "wadj[1]")):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32
-                    and t.is_contiguous() and t.numel() == col.numel()):
-                raise TypeError("%s must be a contiguous CUDA int32 tensor shaped like col" % nm)
+        like_col(cs, "wadj[0]")
+        like_col(wcdf, "wadj[1]")
         check(_lib.lib().come_random_walks_w(
             ptr(rowptr), ptr(cs), ptr(wcdf), V, ptr(starts), P, int(path_length), float(alpha),
             float(p), float(q), int(seed) & (2 ** 64 - 1), int(walk_offset),
@@ -421,13 +428,9 @@ def device_walks(rowptr, col, starts, path_length, alpha=0.0, seed=0, walk_offse
     if float(p) != 1.0 or float(q) != 1.0:
         if col_sorted is None:
             col_sorted = sorted_adjacency(rowptr, col)
-        elif not (isinstance(col_sorted, torch.Tensor) and col_sorted.is_cuda
-                  and col_sorted.dtype == torch.int32 and col_sorted.is_contiguous()
-                  and col_sorted.numel() == col.numel()):
-            raise TypeError("col_sorted must be a contiguous CUDA int32 tensor shaped like col")
-        if trials_out is not None and not (trials_out.is_cuda and trials_out.numel() == 1
-                                           and trials_out.dtype == torch.int64):
-            raise TypeError("trials_out must be a CUDA int64 tensor of one element")
+        else:
+            like_col(col_sorted, "col_sorted")
+        check_trials_out()
         check(_lib.lib().come_random_walks_pq(
             ptr(rowptr), ptr(col), ptr(col_sorted), V, ptr(starts), P, int(path_length),
             float(alpha), float(p), float(q), int(seed) & (2 ** 64 - 1), int(walk_offset),

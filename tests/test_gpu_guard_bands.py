@@ -452,21 +452,43 @@ def test_hot_rows(V):
     assert torch.equal(counts.long(), torch.bincount(table.long(), minlength=V))
 
 
-@pytest.mark.parametrize("staged", [0, 1])
-@pytest.mark.parametrize("P,Lw", [(1, 1), (257, 17)])
+@pytest.mark.parametrize("P,Lw,staged", [(1, 1, 0), (257, 17, 0), (1, 1, 1), (257, 17, 1),
+                                         (257, 17, "pq"), (257, 17, "w")])
 def test_random_walks(P, Lw, staged):
+    """come_random_walks with direct (0) and LDS-staged (1) stores, and the two other entry points
+    of the staged launch body, come_random_walks_pq and come_random_walks_w, at (p, q) = (0.25, 4)."""
     Vg = 50
     rng = np.random.RandomState(P)
     deg = rng.randint(0, 5, Vg)  # some nodes without neighbours: their walks end early
-    rowptr = torch.as_tensor(np.concatenate([[0], np.cumsum(deg)]).astype(np.int64), device=dev())
-    col = torch.as_tensor(rng.randint(0, Vg, max(1, int(deg.sum()))).astype(np.int32), device=dev())
+    rowptr_h = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+    col_h = rng.randint(0, Vg, max(1, int(deg.sum()))).astype(np.int32)
+    rowptr = torch.as_tensor(rowptr_h, device=dev())
+    col = torch.as_tensor(col_h, device=dev())
     starts = torch.as_tensor(rng.randint(0, Vg, P).astype(np.int32), device=dev())
-    c = Call("come_random_walks P=%d L=%d staged=%d" % (P, Lw, staged))
+    c = Call("come_random_walks P=%d L=%d staged=%s" % (P, Lw, staged))
     c.const(rowptr, col, starts)
-    out = c.out((P, Lw), torch.int32, 128 * Lw * 4)
-    with options(walk_staged=staged):
-        ok(_lib.lib().come_random_walks(ptr(rowptr), ptr(col), Vg, ptr(starts), P, Lw, 0.1, 12345,
-                                        0, None, ptr(out), stream_handle(out.device)), c.what)
+    if staged in (0, 1):
+        out = c.out((P, Lw), torch.int32, 128 * Lw * 4)
+        with options(walk_staged=staged):
+            ok(_lib.lib().come_random_walks(ptr(rowptr), ptr(col), Vg, ptr(starts), P, Lw, 0.1,
+                                            12345, 0, None, ptr(out), stream_handle(out.device)),
+               c.what)
+    else:
+        from come_amd import cpu
+        ascending = cpu.sorted_adjacency(rowptr_h, col_h)
+        if staged == "pq":
+            third = torch.as_tensor(ascending, device=dev())
+            entry, adj = _lib.lib().come_random_walks_pq, col
+        else:
+            w = rng.lognormal(0.0, 1.0, len(col_h)).astype(np.float32)
+            third = torch.as_tensor(cpu.walk_cdf(rowptr_h, w).view(np.int32), device=dev())
+            entry, adj = _lib.lib().come_random_walks_w, torch.as_tensor(ascending, device=dev())
+        c.const(third, adj)
+        out = c.out((P, Lw), torch.int32, 128 * Lw * 4)
+        trials = c.out((1,), torch.int64, 4096)
+        trials.zero_()
+        ok(entry(ptr(rowptr), ptr(adj), ptr(third), Vg, ptr(starts), P, Lw, 0.1, 0.25, 4.0, 12345,
+                 0, None, ptr(out), ptr(trials), stream_handle(out.device)), c.what)
     c.done()
     assert int(out.min()) >= -1 and int(out.max()) < Vg
 

@@ -3,11 +3,14 @@ the walk's start (graph_utils.py:36-45), walks do not depend on how they are spl
 and the step distribution is the reference walker's (uniform neighbour, restart with probability
 alpha) -- a statistical parity test, since the device stream is Philox, not CPython's MT19937
 (the exact stream is the host path, tests/test_walks.py)."""
+import functools
+
 import numpy as np
 import pytest
 
+from come_amd import cpu
 from come_amd import graph_utils as gu
-from come_amd._lib import options
+from come_amd._lib import ComeError, options
 from come_amd.graph import chung_lu
 
 torch = pytest.importorskip("torch")
@@ -132,7 +135,7 @@ def test_staged_output_matches_direct_stores(P, L):
     emit = (torch.arange(V, device=d, dtype=torch.int32) * 5 + 2).contiguous()
     for kw in ({}, {"emit": emit}):
         out = []
-        for opt in (0, 1, 2, 3):  # direct, then 16-, 8- and 32-step LDS slices
+        for opt in (0, 1):  # direct, then LDS-staged
             with options(walk_staged=opt):
                 out.append(gu.device_walks(rowptr_t, col, starts, L, alpha=0.15, seed=7,
                                            walk_offset=5, **kw))
@@ -140,6 +143,74 @@ def test_staged_output_matches_direct_stores(P, L):
             assert torch.equal(out[0], o), (P, L, kw.keys())
         w = out[1].cpu().numpy()
         assert (w[::11] == -1).all()
+    for opt in (2, 3):  # the retired 8- and 32-step slices: refused at the launch
+        with options(walk_staged=opt):
+            with pytest.raises(ComeError, match="walk_staged"):
+                gu.device_walks(rowptr_t, col, starts, L, alpha=0.15, seed=7, walk_offset=5)
+
+
+@functools.lru_cache(maxsize=None)
+def staged_edges_inputs():
+    """chung_lu(2000, 5) with three isolated nodes appended, rows ascending, seeded log-normal
+    weights and their thresholds, 513 starts (-1, V and an isolated node among them) and an emit
+    map, on the host and on the device; built once and never modified."""
+    d = dev()
+    g = chung_lu(2000, 5.0)
+    rowptr = np.ascontiguousarray(np.concatenate([g.rowptr, [g.rowptr[-1]] * 3]), np.int64)
+    V = len(rowptr) - 1
+    rng = np.random.RandomState(16)
+    col, w = cpu.sort_weighted_adjacency(
+        rowptr, g.col.astype(np.int32), rng.lognormal(0.0, 1.5, len(g.col)).astype(np.float32))
+    starts = rng.randint(0, V, 513).astype(np.int32)
+    starts[::7] = V - 1 - (np.arange(len(starts[::7])) % 3)  # isolated: the walk ends at once
+    starts[1::11] = -1  # not a node: an empty walk
+    starts[2::13] = V
+    for P in (255, 256, 257, 513):  # the last row of each launch's last workgroup is a walk
+        starts[P - 1] = P
+    host = dict(rowptr=rowptr, col=col, wcdf=cpu.walk_cdf(rowptr, w).view(np.int32), starts=starts,
+                emit=(np.arange(V) * 5 + 2).astype(np.int32))
+    return host, {k: torch.from_numpy(v).to(d) for k, v in host.items()}
+
+
+def test_three_entry_points_through_the_staged_bodys_edges():
+    """The one staged launch body under its three step policies at its edges: a last chunk of
+    exactly 16 steps (L = 16, 32), one step short and one over (15, 17, 33), a last workgroup of
+    exactly 256 rows (P = 256), of 255 and of 1 (257, 513).  Bit-exact against the independent
+    restatement (first order) and the CPU twins (pq, weighted; trial counts too), every cell of a
+    sentinel-filled `out` written."""
+    from oracle import oracle as orc
+    host, t = staged_edges_inputs()
+    seed, off, alpha, sentinel = 2 ** 40 + 16, 2 ** 33 + 5, 0.15, -7
+    wcdf = host["wcdf"].view(np.uint32)
+    dead = 0
+    for P in (255, 256, 257, 513):
+        hs, ds = np.ascontiguousarray(host["starts"][:P]), t["starts"][:P].contiguous()
+        for L in (15, 16, 17, 32, 33):
+            for em in (None, "emit"):
+                he, de = (None, None) if em is None else (host[em], t[em])
+                kw = dict(alpha=alpha, seed=seed, walk_offset=off)
+                refs = {"first": (orc.philox_walks(host["rowptr"], host["col"], hs, L, alpha,
+                                                   seed=seed, walk_offset=off, emit=he), None),
+                        "pq": cpu.random_walks_pq(host["rowptr"], host["col"], hs, L, p=0.25, q=4.0,
+                                                  emit=he, return_trials=True, threads=2, **kw),
+                        "w": cpu.random_walks_w(host["rowptr"], host["col"], wcdf, hs, L, p=0.25,
+                                                q=4.0, emit=he, return_trials=True, threads=2,
+                                                **kw)}
+                for name, extra in (("first", {}), ("pq", dict(p=0.25, q=4.0, col_sorted=t["col"])),
+                                    ("w", dict(p=0.25, q=4.0, wadj=(t["col"], t["wcdf"])))):
+                    out = torch.full((P, L), sentinel, dtype=torch.int32, device=ds.device)
+                    trials = torch.zeros(1, dtype=torch.int64, device=ds.device)
+                    if name != "first":
+                        extra["trials_out"] = trials
+                    got = gu.device_walks(t["rowptr"], t["col"], ds, L, emit=de, out=out, **kw,
+                                          **extra).cpu().numpy()
+                    ref, ref_trials = refs[name]
+                    assert (got != sentinel).all(), (name, P, L, em)
+                    np.testing.assert_array_equal(got, ref, err_msg=str((name, P, L, em)))
+                    if ref_trials is not None:
+                        assert int(trials) == ref_trials > 0, (name, P, L, em)
+                    dead += int((ref == -1).sum())
+    assert dead > 0
 
 
 @pytest.mark.parametrize("alpha,L,offset", [(0.0, 80, 0), (0.15, 33, 5_000_000_123), (1.0, 7, 5)])
