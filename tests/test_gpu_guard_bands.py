@@ -452,6 +452,24 @@ def test_hot_rows(V):
     assert torch.equal(counts.long(), torch.bincount(table.long(), minlength=V))
 
 
+@pytest.mark.parametrize("V", [31, 32, 33])
+def test_quiet_rows(V):
+    table = torch.as_tensor(np.random.RandomState(V).randint(0, V, 5000).astype(np.int32),
+                            device=dev())
+    c = Call("come_quiet_rows V=%d" % V)
+    c.const(table)
+    counts = c.out((V,), torch.int32, 4096)
+    total = c.out((1,), torch.float64, 4096)
+    bits = c.out(((V + 31) // 32,), torch.int32, 4096)
+    # ~161 slots a row: about half the rows' successors are at or below the bound of 160
+    ok(_lib.lib().come_quiet_rows(ptr(table), table.numel(), V, 1.0, 1, 5000.0 / 160.0, 1.0, 175,
+                                  ptr(counts), ptr(total), ptr(bits), stream_handle(table.device)),
+       c.what)
+    c.done()
+    assert torch.equal(counts.long(), torch.bincount(table.long(), minlength=V))
+    assert float(total[0]) == 5000.0
+
+
 @pytest.mark.parametrize("P,Lw,staged", [(1, 1, 0), (257, 17, 0), (1, 1, 1), (257, 17, 1),
                                          (257, 17, "pq"), (257, 17, "w")])
 def test_random_walks(P, Lw, staged):

@@ -13,7 +13,8 @@ Bars:
   * contended rows (float-atomic deltas instead of fma write-backs) on one wavefront: tier B,
     <= 1e-3 abs, most elements within 1e-5;
   * the library-derived contended-row bitmap (hot="auto" / hot_rows == NULL, plain and packed
-    table) equals the explicit come_hot_rows bitmap at DEFAULT_HOT_P.
+    table) equals the explicit come_hot_rows bitmap at DEFAULT_HOT_P, also where thousands of
+    rows sit right at the threshold, the table ends inside a wavefront, and one flipped bit shows.
 """
 import numpy as np
 import pytest
@@ -22,6 +23,7 @@ import torch
 from oracle import oracle as orc
 
 import come_amd.training_sdg_inner as tsi
+import quiet_rule as qr
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -182,6 +184,76 @@ def test_derived_hot_bitmap_matches_explicit(d):
         np.testing.assert_array_equal(got[1], ref[1])
     cold = run(node0, ctx0, walks, seeds, w, n, tab, 0.1, tsi.MODE_HOGWILD, None, opts)
     assert not np.array_equal(cold[1], ref[1])
+
+
+def derived_against_explicit(V, L, T, counts, d=128, w=3, n=0):
+    """One Hogwild launch over disjoint (permutation) walks with the explicit come_hot_rows bitmap
+    at the library's own threshold, and the same launch with hot="auto" on the plain and on the
+    packed table: bit for bit the same tables.  Returns what a caller needs to go on."""
+    rng = np.random.RandomState(V + T % 1000)
+    table = orc.make_table(counts, T)
+    slots = qr.table_counts(table, V)
+    node0 = rng.uniform(-1, 1, (V, d)).astype(np.float32)
+    ctx0 = rng.uniform(-0.3, 0.3, (V, d)).astype(np.float32)
+    walks = rng.permutation(V).reshape(V // L, L).astype(np.int32)
+    seeds = rng.randint(0, 2 ** 48, V // L, dtype=np.int64).astype(np.uint64)
+    tab = dev(table)
+    packed = tsi.pack_table(tab)
+    assert packed is not None and packed.words.shape[0] == (T + 63) // 64 and T % 64 != 0
+    min_count = max(1, int(tsi.default_hot_share(d) * T))
+    explicit = tsi.hot_rows(tab, V, min_count)
+    np.testing.assert_array_equal(explicit.cpu().numpy().view(np.uint32),
+                                  qr.pack_bits(qr.hot_bits(slots, min_count)))
+
+    def launch(t, hot):
+        return run(node0, ctx0, walks, seeds, w, n, t, 0.1, tsi.MODE_HOGWILD, hot,
+                   {"o2_kernel": 3})
+
+    ref = launch(tab, explicit)
+    for t in (tab, packed):
+        got = launch(t, "auto")
+        np.testing.assert_array_equal(got[0], ref[0])
+        np.testing.assert_array_equal(got[1], ref[1])
+    return slots, min_count, explicit, ref, lambda hot: launch(tab, hot)
+
+
+def test_derived_hot_bitmap_next_to_its_threshold():
+    """The derived bitmap (k_table_counts / k_table_counts_packed + k_hot_bits inside the launch)
+    where many rows sit right at the threshold: T = 1,000,037 puts it at 5 slots, leaves the last
+    wavefront of the table and the last packed word ragged (T % 64 = 37), and zipf(1.6) counts
+    give 1183 rows exactly 5 slots and 1657 rows 4.  A single wrong bit on either side shows: the
+    explicit bitmap with one 5-slot row cleared, or one 4-slot row set, trains differently."""
+    V, L, T = 32768, 16, 1000037
+    counts = np.random.RandomState(9).zipf(1.6, V).clip(1, 10 ** 6)
+    slots, min_count, explicit, ref, launch = derived_against_explicit(V, L, T, counts)
+    assert min_count == 5
+    at, below = np.flatnonzero(slots == 5), np.flatnonzero(slots == 4)
+    print("%d rows at the threshold of 5 slots, %d rows one below" % (len(at), len(below)))
+    assert len(at) >= 100 and len(below) >= 100
+    host = explicit.cpu().numpy().view(np.uint32)
+    for side, rows in (("cleared", at), ("set", below)):
+        for tries, row in enumerate(rows[:16], 1):  # every row is on a walk; most flips show
+            one_off = host.copy()
+            one_off[row // 32] ^= np.uint32(1 << (row % 32))
+            got = launch(dev(one_off))
+            if not (np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])):
+                break
+        else:
+            raise AssertionError("no single bit %s among 16 rows changed the result" % side)
+        print("one bit %s (row %d, try %d) changes the result" % (side, row, tries))
+
+
+def test_derived_hot_bitmap_at_threshold_1_and_on_a_table_of_one_word():
+    """T = 30,003: the threshold is 1 slot, 32768 rows share fewer slots than there are rows, so
+    thousands hold none and the hot rows are those with any; the last packed word is partial.
+    T = 37: shorter than a wavefront, one partial packed word."""
+    V, T = 32768, 30003
+    counts = np.random.RandomState(9).zipf(1.6, V).clip(1, 10 ** 6)
+    slots, min_count, _, _, _ = derived_against_explicit(V, 16, T, counts)
+    assert min_count == 1 and (slots == 0).sum() >= 100 and (slots > 0).sum() >= 100
+    slots, min_count, _, _, _ = derived_against_explicit(8, 4, 37,
+                                                         np.array([1, 5, 2, 9, 1, 1, 30, 2.]))
+    assert min_count == 1 and 0 < (slots == 0).sum() < 8
 
 
 def test_hot_bitmap_validation():
