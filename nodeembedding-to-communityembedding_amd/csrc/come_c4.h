@@ -1,8 +1,9 @@
 // come_c4.h -- what the C4 kernels share (gfx950): argument blocks, the bf16-part arithmetic,
 // launch constants and the entry points' launch path (launch, with_width).  Included by
 // come_community.hip (community step), come_gmm_estep.hip (GMM responsibilities),
-// come_gmm_scatter.hip (M-step scatter matrices) and come_kmeans.hip (the launch path).  A tuning constant lives in the shape struct
-// that uses it, beside the measurement that chose it; A/B builds go through scripts/build_ab.sh.
+// come_gmm_scatter.hip (M-step scatter matrices), come_gmm_params.hip (M-step parameters) and
+// come_kmeans.hip (the launch path).  A tuning constant lives in the shape struct that uses it,
+// beside the measurement that chose it; A/B builds go through scripts/build_ab.sh.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,26 +1,33 @@
 // come_gmm_scatter.hip -- GMM M-step scatter matrices (gfx950).
 //
-// Replaces the numerator of sklearn's _estimate_gaussian_covariances_full (community_embeddings.py
-// :27 fit): come_gmm_scatter -> k_gmm_cov_fb3 (default at d = 128) and k_gmm_cov_bf3 (d = 64; fp32
-// operands as bf16 parts), k_gmm_cov16 (fp32 MFMA), k_gmm_cov_valu / k_gmm_cov_wide (VALU, any d),
-// k_gmm_cov_reduce (chunk partials in a fixed order).
+// S_k = sum_i resp[i,k] (x_i - mu_k)(x_i - mu_k)^T, the numerator of sklearn's full covariance
+// (_estimate_gaussian_covariances_full: np.dot(resp[:, k] * diff.T, diff) / nk[k];
+// community_embeddings.py:27 fit), 2 V K d^2 flops per M-step.  come_gmm_scatter -> one of five
+// scatter kernels -- k_gmm_cov_fb3 (default at d = 128) and k_gmm_cov_bf3 (d = 64; fp32 operands
+// as bf16 parts), k_gmm_cov16 (fp32 MFMA), k_gmm_cov_valu / k_gmm_cov_wide (VALU, any d) -- then
+// k_gmm_cov_reduce / k_gmm_cov_reduce_upper.  The scatter kernels share one grid: workgroup
+// (component group, row chunk) stages the rows of its chunk through LDS block by block, centred on
+// mu_k, with their weights, sums them for its components and writes its own partial
+// [chunk][K][d][d]; the reducer adds the chunks in chunk order (deterministic, no float atomics).
+// blockIdx.x = component group varies fastest, so the workgroups of one chunk run together and
+// share its rows through L2 / MALL.
+// Shared code: CovArgs, CovChunk (blockIdx -> components and rows), cov_staging (the staging
+// wavefronts' ring of k_gmm_cov16 and k_gmm_cov_bf3), CovBf3Tiles / bf3_mfma6 / cov32_store (the
+// 32-wide bf16-part tiles of k_gmm_cov_bf3 and k_gmm_cov_fb3), cov_chunk_sum (both reducers).
+// come_gmm_params.hip turns the scatter matrices into the mixture's parameters.
 
 #include "come_c4.h"
 
 namespace come {
 
-// ---- GMM M-step scatter matrices -------------------------------------------------------------
-//
-// S_k = sum_i resp[i,k] (x_i - mu_k)(x_i - mu_k)^T, the numerator of sklearn's full covariance
-// (_estimate_gaussian_covariances_full: np.dot(resp[:, k] * diff.T, diff) / nk[k]), 2 V K d^2
-// flops per M-step.  Workgroup (k, chunk): rows of the chunk are staged through LDS in blocks of
-// kCovRB samples, centred on mu_k, with their weights; the reduction over samples is the MFMA
-// k-dimension (v_mfma_f32_32x32x2_f32: lane (r, h) supplies A[c1 = rt*32 + r][sample s0 + h] =
-// w * xc and B[sample s0 + h][c2 = ct*32 + r] = xc).  The D x D output is split into 32 x 32
-// tiles over the 4 wavefronts.  Each chunk writes its own partial; k_gmm_cov_reduce sums the
-// chunks in a fixed order (deterministic, no float atomics).  blockIdx.x = k varies fastest, so
-// the K workgroups of one chunk run together and share its rows through L2 / MALL.
+// The chunk granule: come_gmm_scatter rounds a chunk's row count up to a multiple of it
+// (tests/scatter_models.py rows_per_chunk models the same rounding), so every chunk but the last
+// is whole blocks of each kernel (16, 32 or 64 rows).  It is also k_gmm_cov_valu's block.
 constexpr int kCovRB = 64;
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct CovArgs {
     const float *x;
@@ -35,19 +42,38 @@ struct CovArgs {
                      // reduction mirrors them), no transposed (uncoalesced) stores
 };
 
+// What workgroup (blockIdx.x, blockIdx.y) of a scatter kernel sums, CPW components and RB rows per
+// block: components k0 .. k0 + nk - 1 over rows [c0, c1) of chunk blockIdx.y, nb blocks.
+struct CovChunk {
+    int64_t chunk, c0, c1;
+    int k0, nk, nb;
+    // index of component k0 + tk's partial among the [chunks][K] matrices of a.out
+    __device__ __forceinline__ int64_t part(const CovArgs &a, int tk) const {
+        return chunk * a.K + k0 + tk;
+    }
+};
+
+template <int CPW, int RB>
+__device__ __forceinline__ CovChunk cov_chunk(const CovArgs &a) {
+    const int64_t chunk = blockIdx.y;
+    const int k0 = blockIdx.x * CPW, nk = a.K - k0 < CPW ? a.K - k0 : CPW;
+    const int64_t c0 = chunk * a.rows_per_chunk, c1 = min(c0 + a.rows_per_chunk, a.V);
+    return {chunk, c0, c1, k0, nk, c1 > c0 ? (int)((c1 - c0 + RB - 1) / RB) : 0};
+}
+
 // ---- M-step scatter on v_mfma_f32_16x16x4_f32 (k_gmm_cov16, gmm_cov_async = 3) ----------------
 //
 // 4 MFMA + 4 staging wavefronts, CPW components per workgroup, two image buffers, two workgroups
 // per CU, on 16 x 16 output tiles (only rt <= ct; each off-diagonal tile also stored transposed,
-// so S_k comes out exactly symmetric): the symmetric output needs the
-// 36 upper tiles of 64 at d = 128 (0.5625 of the dense MFMA cycles) instead of 10 of 16 32-wide
-// tiles (0.625).  MFMA (tile rt, ct; 4 samples): A[i][k] = w_s (x_s - mu)[rt*16 + i], B[k][j] =
-// (x_s - mu)[ct*16 + j], lane l: i = j = l % 16, samples s = 16 g + 4 (l / 16) + t for the four
-// steps t of a 16-sample group g, so each operand row of a group is ONE ds_read_b128 of the
-// transposed image B[k][c][s] (rows of 32 samples, 16-byte granules XOR-swizzled by c % 8:
-// conflict-free without padding).  A d = 128 component's 36 tiles split 18 / 18 over two
-// wavefronts by tile rows {0, 1, 6, 7} and {2, 3, 4, 5}; a wavefront weights its 4 A rows once
-// per group and streams the B rows column by column (few VGPRs at 4 waves per SIMD).
+// so S_k comes out exactly symmetric): the symmetric output needs the 36 upper tiles of 64 at
+// d = 128 (0.5625 of the dense MFMA cycles) instead of 10 of 16 32-wide tiles (0.625).  MFMA (tile
+// rt, ct; 4 samples): A[i][k] = w_s (x_s - mu)[rt*16 + i], B[k][j] = (x_s - mu)[ct*16 + j], lane l:
+// i = j = l % 16, samples s = 16 g + 4 (l / 16) + t for the four steps t of a 16-sample group g,
+// so each operand row of a group is ONE ds_read_b128 of the transposed image B[k][c][s] (rows of
+// 32 samples, 16-byte granules XOR-swizzled by c % 8: conflict-free without padding).  A d = 128
+// component's 36 tiles split 18 / 18 over two wavefronts by tile rows {0, 1, 6, 7} and
+// {2, 3, 4, 5}; a wavefront weights its 4 A rows once per group and streams the B rows column by
+// column (few VGPRs at 4 waves per SIMD).
 // (Twice the MFMA wavefronts with half the tiles each -- 4 MFMA waves per SIMD, the E-step /
 // community lesson -- was bit-identical and no faster: 7.45 vs 7.35 ms, profiles/r04_ab_scatter16.txt.)
 template <int D>
@@ -97,10 +123,8 @@ __device__ __forceinline__ int cov16_off(int c, int gran) {  // image offset of 
 
 template <int D, int P>
 __device__ __forceinline__ void cov16_consume(const float *img, int nb, int tk, int lane,
-                                              __attribute__((ext_vector_type(4)))
-                                              float (&acc)[Cov16<D>::NTW]) {
+                                              f32x4 (&acc)[Cov16<D>::NTW]) {
     using C = Cov16<D>;
-    using f32x4 = __attribute__((ext_vector_type(4))) float;
     constexpr Cov16Tiles<D> TT{};
     const int j16 = lane & 15, kg = lane >> 4;
     for (int j = 0; j < nb; ++j) {
@@ -137,18 +161,17 @@ __device__ __forceinline__ void cov16_consume(const float *img, int nb, int tk, 
 
 // the MFMA part of wavefront part P (compile-time tile tables): consume, then store the tiles
 template <int D, int P>
-__device__ __forceinline__ void cov16_part(const CovArgs &a, const float *img, int nb, int tk,
-                                           int nk, int k0, int64_t chunk, int lane) {
+__device__ __forceinline__ void cov16_part(const CovArgs &a, const float *img, const CovChunk &ch,
+                                           int tk, int lane) {
     using C = Cov16<D>;
-    using f32x4 = __attribute__((ext_vector_type(4))) float;
     f32x4 acc[C::NTW];
 #pragma unroll
     for (int n = 0; n < C::NTW; ++n) acc[n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    if (nb > 0) cov16_consume<D, P>(img, nb, tk, lane, acc);
-    if (tk >= nk) return;  // wavefront-uniform: K not a multiple of CPW
+    if (ch.nb > 0) cov16_consume<D, P>(img, ch.nb, tk, lane, acc);
+    if (tk >= ch.nk) return;  // wavefront-uniform: K not a multiple of CPW
     constexpr Cov16Tiles<D> TT{};
     const int j16 = lane & 15, kg = lane >> 4;
-    float *out = a.out + (chunk * a.K + k0 + tk) * D * D;
+    float *out = a.out + ch.part(a, tk) * D * D;
 #pragma unroll
     for (int n = 0; n < C::NTW; ++n) {
         const int rt = TT.rows[P][TT.slot[P][n]], ct = TT.ct[P][n];
@@ -163,7 +186,7 @@ __device__ __forceinline__ void cov16_part(const CovArgs &a, const float *img, i
 }
 
 // k_gmm_cov16's staging wavefronts (256 threads, thread st): block blk of the chunk [c0, c1) goes
-// global -> VGPR register set u (three sets: loads run 3 blocks ahead of the stage that consumes
+// global -> VGPR register set u (NS sets: loads run NS blocks ahead of the stage that consumes
 // them, an HBM / MALL round trip under load exceeding one block period) -> centred, transposed
 // LDS image per component (stage), with the weights beside it.
 // d = 128: 16-byte loads.  Thread st < RB D / 16 owns feature quad fq = st / 8 (features 4 fq ..
@@ -176,22 +199,20 @@ __device__ __forceinline__ void cov16_part(const CovArgs &a, const float *img, i
 template <int D>
 struct Cov16StageX4 {
     using C = Cov16<D>;
-    using f32x4 = __attribute__((ext_vector_type(4))) float;
     static constexpr int RB = C::RB, CPW = C::CPW, NX = RB * D / 16;
     static_assert(RB == 32 && NX <= 256 && CPW * RB <= 256, "x4 staging layout");
     const CovArgs &a;
     const int sg, fq, wk, ws, k0, nk;
-    const bool xl, wlane;
+    const bool xl;
     const int64_t c0, c1;
     // register sets: loads run NS blocks ahead (3 / 4 / 5+: 7.266 / 7.247 ms at C4 / spills)
     static constexpr int NS = 4;
     float mu[CPW][4];
     f32x4 xv[NS][4];
     float wl[NS];
-    __device__ __forceinline__ Cov16StageX4(const CovArgs &a_, int st, int k0_, int nk_, int64_t c0_,
-                                            int64_t c1_)
-        : a(a_), sg(st % 8), fq(st / 8), wk(st % (CPW * RB) / RB), ws(st % RB), k0(k0_), nk(nk_),
-          xl(st < NX), wlane(true), c0(c0_), c1(c1_) {
+    __device__ __forceinline__ Cov16StageX4(const CovArgs &a_, const CovChunk &ch, int st)
+        : a(a_), sg(st % 8), fq(st / 8), wk(st % (CPW * RB) / RB), ws(st % RB), k0(ch.k0),
+          nk(ch.nk), xl(st < NX), c0(ch.c0), c1(ch.c1) {
 #pragma unroll
         for (int kk = 0; kk < CPW; ++kk)
 #pragma unroll
@@ -201,7 +222,7 @@ struct Cov16StageX4 {
     // Loads are unconditional (rows past the chunk clamped to its last row, components past K
     // to K - 1) and the out-of-range values zeroed when staged: a load under a divergent branch
     // leaves the compiler unable to count the loads in flight, and it then waits for all of them
-    // (vmcnt(0)) before every stage -- the three-block lookahead collapses to none.
+    // (vmcnt(0)) before every stage -- the lookahead collapses to none.
     __device__ __forceinline__ void load(int u, int blk) {
         const int64_t b = c0 + (int64_t)blk * RB;
 #pragma unroll
@@ -240,21 +261,18 @@ struct Cov16StageX4 {
 template <int D>
 struct Cov16StageCol {
     using C = Cov16<D>;
-    using f32x4 = __attribute__((ext_vector_type(4))) float;
     static constexpr int RB = C::RB, CPW = C::CPW, SPT = RB * D / 256;
     static_assert(SPT % 4 == 0 && SPT * CPW <= 64 && D % 64 == 0, "staging layout");
     const CovArgs &a;
     const int sc, sp, wk, ws, k0, nk;
-    const bool wlane;
     const int64_t c0, c1;
     static constexpr int NS = 3;
     float mu[CPW];
-    float xv[3][SPT];
-    float wl[3];
-    __device__ __forceinline__ Cov16StageCol(const CovArgs &a_, int st, int lane, int k0_, int nk_,
-                                             int64_t c0_, int64_t c1_)
-        : a(a_), sc(st % D), sp(st / D), wk(lane % (SPT * CPW) / SPT), ws(lane % SPT), k0(k0_),
-          nk(nk_), wlane(true), c0(c0_), c1(c1_) {
+    float xv[NS][SPT];
+    float wl[NS];
+    __device__ __forceinline__ Cov16StageCol(const CovArgs &a_, const CovChunk &ch, int st)
+        : a(a_), sc(st % D), sp(st / D), wk((st & 63) % (SPT * CPW) / SPT), ws((st & 63) % SPT),
+          k0(ch.k0), nk(ch.nk), c0(ch.c0), c1(ch.c1) {
 #pragma unroll
         for (int kk = 0; kk < CPW; ++kk)
             mu[kk] = kk < nk ? a.means[(int64_t)(k0 + kk) * D + sc] : 0.0f;
@@ -286,16 +304,18 @@ struct Cov16StageCol {
     }
 };
 
-// the staging pipeline: block j + 1 is staged while block j is multiplied (two image buffers, one
-// barrier per block); register set (j + 1) % NS holds block j + 1, reloaded with block j + 1 + NS.
+// The staging wavefronts' pipeline over a ring of NBUF image buffers (S::stage writes block blk
+// into buffer blk % NBUF): block j + NBUF - 1 is staged while block j is multiplied, one barrier
+// per block; register set (j + NBUF - 1) % NS holds that block and is reloaded with the block NS
+// further on.
 // Every load and stage is issued unconditionally (the block index clamped to nb - 1; a stage of
 // block nb lands in a buffer nobody reads again, its values zeroed): with no branch around them
 // the compiler counts the loads in flight exactly and each stage waits only for its own set
 // (a conditional load made it drain all of them, vmcnt(0), at the loop head).
-template <int D, typename S>
-__device__ __forceinline__ void cov16_staging(float *img, S &sg, int nb) {
+template <int NBUF, typename S>
+__device__ __forceinline__ void cov_staging(float *img, S &sg, int nb) {
     if (nb == 0) return;
-    constexpr int SD = Cov16<D>::NBUF - 1, NS = S::NS;
+    constexpr int SD = NBUF - 1, NS = S::NS;
     const int last = nb - 1;
 #pragma unroll
     for (int u = 0; u < NS; ++u) sg.load(u, min(u, last));
@@ -318,35 +338,20 @@ template <int D>
 __global__ void __launch_bounds__((Cov16<D>::THREADS))
     __attribute__((amdgpu_waves_per_eu(4))) k_gmm_cov16(CovArgs a) {
     using C = Cov16<D>;
-    constexpr int CPW = C::CPW;
-    constexpr int RB = C::RB;
     static_assert(C::NBUF * C::BUF * sizeof(float) * 2 <= 160 * 1024, "two workgroups per CU");
     __shared__ __attribute__((aligned(16))) float img[C::NBUF * C::BUF];
-    const int64_t chunk = blockIdx.y;
-    const int k0 = blockIdx.x * CPW;
-    const int nk = a.K - k0 < CPW ? a.K - k0 : CPW;
-    const int64_t c0 = chunk * a.rows_per_chunk;
-    int64_t c1 = c0 + a.rows_per_chunk;
-    if (c1 > a.V) c1 = a.V;
-    const int nb = c1 > c0 ? (int)((c1 - c0 + RB - 1) / RB) : 0;
+    const CovChunk ch = cov_chunk<C::CPW, C::RB>(a);
     const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     if (wid < C::AW) {
         // ---- MFMA wavefronts: component tk, tile part p ----
         const int tk = wid / C::WPC, p = wid % C::WPC;
-        constexpr int P1 = C::WPC > 1 ? 1 : 0;
-        if (p == 0) cov16_part<D, 0>(a, img, nb, tk, nk, k0, chunk, lane);
-        else cov16_part<D, P1>(a, img, nb, tk, nk, k0, chunk, lane);
+        if (p == 0) cov16_part<D, 0>(a, img, ch, tk, lane);
+        else cov16_part<D, C::WPC - 1>(a, img, ch, tk, lane);
         return;
     }
     // ---- staging wavefronts: 16-byte loads at d = 128, one column per thread at d = 64 ----
-    const int st = tid - 64 * C::AW;
-    if constexpr (D == 128) {
-        Cov16StageX4<D> sg(a, st, k0, nk, c0, c1);
-        cov16_staging<D>(img, sg, nb);
-    } else {
-        Cov16StageCol<D> sg(a, st, lane, k0, nk, c0, c1);
-        cov16_staging<D>(img, sg, nb);
-    }
+    std::conditional_t<D == 128, Cov16StageX4<D>, Cov16StageCol<D>> sg(a, ch, tid - 64 * C::AW);
+    cov_staging<C::NBUF>(img, sg, ch.nb);
 }
 
 // ---- M-step scatter on bf16-part MFMAs (k_gmm_cov_bf3, gmm_cov_async = 4) --------------------
@@ -378,7 +383,8 @@ struct CovBf3 {
     static constexpr int PLANE = D * RB * 2;        // bytes per part image (D rows x 32 bf16)
     static constexpr int IMG = 3 * PLANE;           // per component (24 KB at d = 128)
     static constexpr int BUF = CPW * IMG;
-    static constexpr int LDS_BYTES = 2 * BUF;       // 96 KB: one workgroup per CU
+    static constexpr int NBUF = 2;                  // image buffers (cov_staging's ring)
+    static constexpr int LDS_BYTES = NBUF * BUF;    // 96 KB: one workgroup per CU
     static constexpr int SPT = RB * D / (64 * SW);  // samples per staging thread (16 / 8)
     static_assert(SPT % 8 == 0, "a staging thread fills whole 8-sample granules");
     // granule swizzle: bit 0 = bit 2 of the row, bit 1 = bit 1 ^ bit 3 -- distinct over the rows
@@ -397,6 +403,7 @@ template <int D>
 struct CovBf3Tiles {
     int cnt[2], ta[2][5], tb[2][5];
     bool need[2][4];  // fragments a part reads
+    static constexpr int NDG = 2;  // diagonal tiles per part
     constexpr CovBf3Tiles() : cnt(), ta(), tb(), need() {
         // d = 128: 10 upper tiles per component, 5 / 5 over 2 wavefronts
         const int a2[2][5] = {{0, 0, 0, 0, 3}, {1, 1, 1, 2, 2}};
@@ -428,12 +435,46 @@ struct CovBf3Tiles {
     }
 };
 
+// acc += the six part products of order <= 2 of an off-diagonal tile (come_c4.h), smallest first:
+// a3 b1, a2 b2, a1 b3, a2 b1, a1 b2, a1 b1 (A, B: the three parts of the row / column fragment)
+__device__ __forceinline__ void bf3_mfma6(f32x16 &acc, const bf16x8 (&A)[3], const bf16x8 (&B)[3]) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[2], B[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], B[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[2], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[1], B[0], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[1], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[0], B[0], acc, 0, 0, 0);
+}
+
+// row of accumulator register r of a 32x32 MFMA tile in lane (i, h = lane / 32); its column is i
+__device__ __forceinline__ int cov32_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// Lane (i, h) stores the tiles of MFMA part P (CovBf3Tiles) into one component's partial `out`, an
+// off-diagonal tile into its mirror image too unless the reduction mirrors it (upper_only).  (By
+// value and the flag read once: other spellings move k_gmm_cov_fb3's LDS / wait counts.)
+template <int D, int P, int NT>
+__device__ __forceinline__ void cov32_store(const CovArgs &a, float *out, const f32x16 (&acc)[NT],
+                                            int i, int h) {
+    constexpr CovBf3Tiles<D> TT{};
+    static_assert(NT == TT.cnt[P], "one accumulator per tile of the part");
+    const bool mirror = !a.upper_only;
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        const int ta = TT.ta[P][n], tb = TT.tb[P][n];
+        const int jj = 32 * tb + i;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int ii = 32 * ta + cov32_row(r, h);
+            out[(int64_t)ii * D + jj] = acc[n][r];
+            if (ta != tb && mirror) out[(int64_t)jj * D + ii] = acc[n][r];
+        }
+    }
+}
+
 template <int D, int P>
-__device__ __forceinline__ void covbf3_part(const CovArgs &a, const char *smb, int nb, int tk,
-                                            int nk, int k0, int64_t chunk, int lane) {
+__device__ __forceinline__ void covbf3_part(const CovArgs &a, const char *smb, const CovChunk &ch,
+                                            int tk, int lane) {
     using C = CovBf3<D>;
-    using f32x16 = __attribute__((ext_vector_type(16))) float;
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
     constexpr CovBf3Tiles<D> TT{};
     constexpr int NT = TT.cnt[P];
     const int i = lane & 31, h = lane >> 5;
@@ -446,15 +487,15 @@ __device__ __forceinline__ void covbf3_part(const CovArgs &a, const char *smb, i
     // squares on the diagonal of S_k: added to acc block by block it falls under half an ulp of
     // S_ii after about a thousand rows of a chunk and vanishes from then on, in every chunk alike
     // (S_ii 2.2e-6 low at 6 135 rows per chunk).  The other part products have zero mean there.
-    constexpr int NDG = 2;  // diagonal tiles per part
+    constexpr int NDG = TT.NDG;
     f32x16 accd[NDG];
 #pragma unroll
     for (int n = 0; n < NDG; ++n)
 #pragma unroll
         for (int e = 0; e < 16; ++e) accd[n][e] = 0.0f;
-    for (int j = 0; j < nb; ++j) {
+    for (int j = 0; j < ch.nb; ++j) {
         __syncthreads();  // barrier j: block j staged
-        const char *im = smb + (j & 1) * C::BUF + tk * C::IMG;
+        const char *im = smb + (j % C::NBUF) * C::BUF + tk * C::IMG;
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
             bf16x8 F[C::NF][3];
@@ -468,13 +509,13 @@ __device__ __forceinline__ void covbf3_part(const CovArgs &a, const char *smb, i
 #pragma unroll
             for (int n = 0; n < NT; ++n) {
                 const int ta = TT.ta[P][n], tb = TT.tb[P][n];
-                acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][2], F[tb][0], acc[n], 0, 0, 0);
-                if (ta == tb) {
-                    const int dg = TT.dslot(P, n);
-                    accd[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], accd[dg], 0, 0, 0);
-                } else {
-                    acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], acc[n], 0, 0, 0);
+                if (ta != tb) {
+                    bf3_mfma6(acc[n], F[ta], F[tb]);
+                    continue;
                 }
+                const int dg = TT.dslot(P, n);  // the six in the same order, a2 b2 into accd
+                acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][2], F[tb][0], acc[n], 0, 0, 0);
+                accd[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], accd[dg], 0, 0, 0);
                 acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][2], acc[n], 0, 0, 0);
                 acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][0], acc[n], 0, 0, 0);
                 acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][1], acc[n], 0, 0, 0);
@@ -482,20 +523,11 @@ __device__ __forceinline__ void covbf3_part(const CovArgs &a, const char *smb, i
             }
         }
     }
-    if (tk >= nk) return;  // wavefront-uniform: K not a multiple of CPW
-    float *out = a.out + (chunk * a.K + k0 + tk) * D * D;
+    if (tk >= ch.nk) return;  // wavefront-uniform: K not a multiple of CPW
 #pragma unroll
-    for (int n = 0; n < NT; ++n) {
-        const int ta = TT.ta[P][n], tb = TT.tb[P][n];
-        if (ta == tb) acc[n] += accd[TT.dslot(P, n)];
-        const int jj = 32 * tb + i;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ii = 32 * ta + (r & 3) + 8 * (r >> 2) + 4 * h;
-            out[(int64_t)ii * D + jj] = acc[n][r];
-            if (ta != tb && !a.upper_only) out[(int64_t)jj * D + ii] = acc[n][r];
-        }
-    }
+    for (int n = 0; n < NT; ++n)
+        if (TT.ta[P][n] == TT.tb[P][n]) acc[n] += accd[TT.dslot(P, n)];
+    cov32_store<D, P>(a, a.out + ch.part(a, tk) * D * D, acc, i, h);
 }
 
 // staging thread st: feature f = st % D of samples SPT sg .. SPT sg + SPT - 1 (sg = st / D,
@@ -514,10 +546,9 @@ struct CovBf3Stage {
     float mu[CPW];
     float xv[NS][SPT];
     float wv[NS];
-    __device__ __forceinline__ CovBf3Stage(const CovArgs &a_, int st, int lane_, int k0_, int nk_,
-                                           int64_t c0_, int64_t c1_)
-        : a(a_), f(st % D), sg(__builtin_amdgcn_readfirstlane(st / D)), k0(k0_), nk(nk_),
-          lane(lane_), c0(c0_), c1(c1_) {
+    __device__ __forceinline__ CovBf3Stage(const CovArgs &a_, const CovChunk &ch, int st)
+        : a(a_), f(st % D), sg(__builtin_amdgcn_readfirstlane(st / D)), k0(ch.k0), nk(ch.nk),
+          lane(st & 63), c0(ch.c0), c1(ch.c1) {
 #pragma unroll
         for (int kk = 0; kk < CPW; ++kk)
             mu[kk] = kk < nk ? a.means[(int64_t)(k0 + kk) * D + f] : 0.0f;
@@ -538,7 +569,7 @@ struct CovBf3Stage {
         return (l / SPT < nk && row < c1) ? sqrtf(wv[u]) : 0.0f;
     }
     __device__ __forceinline__ void stage(float *img, int u, int blk) const {
-        char *buf = reinterpret_cast<char *>(img) + (blk % 2) * C::BUF;
+        char *buf = reinterpret_cast<char *>(img) + (blk % C::NBUF) * C::BUF;
         const float w = weight(u, blk);
 #pragma unroll
         for (int kk = 0; kk < CPW; ++kk) {
@@ -572,25 +603,16 @@ __global__ void __launch_bounds__(CovBf3<D>::THREADS) __attribute__((amdgpu_wave
     k_gmm_cov_bf3(CovArgs a) {
     using C = CovBf3<D>;
     extern __shared__ __attribute__((aligned(16))) char smb[];
-    const int64_t chunk = blockIdx.y;
-    const int k0 = blockIdx.x * C::CPW;
-    const int nk = a.K - k0 < C::CPW ? a.K - k0 : C::CPW;
-    const int64_t c0 = chunk * a.rows_per_chunk;
-    int64_t c1 = c0 + a.rows_per_chunk;
-    if (c1 > a.V) c1 = a.V;
-    const int nb = c1 > c0 ? (int)((c1 - c0 + C::RB - 1) / C::RB) : 0;
+    const CovChunk ch = cov_chunk<C::CPW, C::RB>(a);
     const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     if (wid < C::AW) {
         const int tk = wid / C::WPC, p = wid % C::WPC;
-        if (p == 0) covbf3_part<D, 0>(a, smb, nb, tk, nk, k0, chunk, lane);
-        else covbf3_part<D, C::WPC - 1>(a, smb, nb, tk, nk, k0, chunk, lane);
+        if (p == 0) covbf3_part<D, 0>(a, smb, ch, tk, lane);
+        else covbf3_part<D, C::WPC - 1>(a, smb, ch, tk, lane);
         return;
     }
-    // cov16_staging's look-ahead is Cov16<D>::NBUF - 1 blocks, while CovBf3Stage::stage and
-    // covbf3_part index the image buffers by blk % 2 / j & 1: the two must agree
-    static_assert(Cov16<D>::NBUF == 2, "k_gmm_cov_bf3 assumes two image buffers");
-    CovBf3Stage<D> sg(a, tid - 64 * C::AW, lane, k0, nk, c0, c1);
-    cov16_staging<D>(reinterpret_cast<float *>(smb), sg, nb);
+    CovBf3Stage<D> sg(a, ch, tid - 64 * C::AW);
+    cov_staging<C::NBUF>(reinterpret_cast<float *>(smb), sg, ch.nb);
 }
 
 // ---- M-step scatter with the staging inside the MFMA wavefronts (k_gmm_cov_fb3, d = 128) -------
@@ -633,17 +655,15 @@ struct CovFb3 {
 };
 
 template <int D, int P>
-__device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, int nb, int k0, int nk,
-                                               int64_t c0, int64_t c1, int64_t chunk, int wid,
-                                               int lane) {
+__device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, const CovChunk &cc,
+                                            int wid, int lane) {
     using C = CovFb3<D>;
-    using f32x4 = __attribute__((ext_vector_type(4))) float;
-    using f32x16 = __attribute__((ext_vector_type(16))) float;
-    typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
     typedef short s16x4 __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
     constexpr CovBf3Tiles<D> TT{};
     constexpr int NT = TT.cnt[P], NS = C::NS;
+    const int nb = cc.nb, k0 = cc.k0, nk = cc.nk;
+    const int64_t c0 = cc.c0, c1 = cc.c1;
     const int tk = wid >> 1;
     const int i = lane & 31, h = lane >> 5;
     // staging role: sample s = 4 wid + lane / 16 of each block, features 8 ch .. 8 ch + 7
@@ -701,7 +721,7 @@ __device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, int nb,
     for (int n = 0; n < NT; ++n)
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[n][e] = 0.0f;
-    constexpr int NDG = 2;  // diagonal tiles per part
+    constexpr int NDG = TT.NDG;
     f32x16 accu[NDG];
 #pragma unroll
     for (int n = 0; n < NDG; ++n)
@@ -735,26 +755,21 @@ __device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, int nb,
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             const int ta = TT.ta[P][n], tb = TT.tb[P][n];
-            if (ta == tb) {
-                // accu = 2 U + a2 b2, halved with the transposition at the end: a2 b2 stays out
-                // of acc (covbf3_part's accd) at no register.  2 a1 is one exponent step up, one
-                // integer add per pair (a zero part becomes 2^-126, whose products vanish).
-                const int dg = TT.dslot(P, n);
-                const uint4 w = __builtin_bit_cast(uint4, F[ta][0]);
-                const bf16x8 a1x2 = __builtin_bit_cast(
-                    bf16x8, uint4{w.x + 0x00800080u, w.y + 0x00800080u, w.z + 0x00800080u,
-                                  w.w + 0x00800080u});
-                accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1x2, F[tb][2], accu[dg], 0, 0, 0);
-                accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1x2, F[tb][1], accu[dg], 0, 0, 0);
-                accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], accu[dg], 0, 0, 0);
-                acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][0], acc[n], 0, 0, 0);
+            if (ta != tb) {
+                bf3_mfma6(acc[n], F[ta], F[tb]);
                 continue;
             }
-            acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][2], F[tb][0], acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][2], acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][0], acc[n], 0, 0, 0);
-            acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][1], acc[n], 0, 0, 0);
+            // accu = 2 U + a2 b2, halved with the transposition at the end: a2 b2 stays out
+            // of acc (covbf3_part's accd) at no register.  2 a1 is one exponent step up, one
+            // integer add per pair (a zero part becomes 2^-126, whose products vanish).
+            const int dg = TT.dslot(P, n);
+            const uint4 w = __builtin_bit_cast(uint4, F[ta][0]);
+            const bf16x8 a1x2 = __builtin_bit_cast(
+                bf16x8, uint4{w.x + 0x00800080u, w.y + 0x00800080u, w.z + 0x00800080u,
+                              w.w + 0x00800080u});
+            accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1x2, F[tb][2], accu[dg], 0, 0, 0);
+            accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1x2, F[tb][1], accu[dg], 0, 0, 0);
+            accu[dg] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][1], F[tb][1], accu[dg], 0, 0, 0);
             acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[ta][0], F[tb][0], acc[n], 0, 0, 0);
         }
     };
@@ -786,24 +801,13 @@ __device__ __forceinline__ void covfb3_body(const CovArgs &a, char *smb, int nb,
             const int dg = TT.dslot(P, n);
             float *u = ut + dg * 32 * 33;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) u[((r & 3) + 8 * (r >> 2) + 4 * h) * 33 + i] = accu[dg][r];
+            for (int r = 0; r < 16; ++r) u[cov32_row(r, h) * 33 + i] = accu[dg][r];
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                acc[n][r] += 0.5f * (accu[dg][r] + u[i * 33 + (r & 3) + 8 * (r >> 2) + 4 * h]);
+                acc[n][r] += 0.5f * (accu[dg][r] + u[i * 33 + cov32_row(r, h)]);
         }
     }
-    float *out = a.out + (chunk * a.K + k0 + tk) * D * D;
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-        const int ta = TT.ta[P][n], tb = TT.tb[P][n];
-        const int jj = 32 * tb + i;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ii = 32 * ta + (r & 3) + 8 * (r >> 2) + 4 * h;
-            out[(int64_t)ii * D + jj] = acc[n][r];
-            if (ta != tb && !a.upper_only) out[(int64_t)jj * D + ii] = acc[n][r];
-        }
-    }
+    cov32_store<D, P>(a, a.out + cc.part(a, tk) * D * D, acc, i, h);
 }
 
 template <int D>
@@ -811,16 +815,10 @@ __global__ void __launch_bounds__(CovFb3<D>::THREADS) __attribute__((amdgpu_wave
     k_gmm_cov_fb3(CovArgs a) {
     using C = CovFb3<D>;
     extern __shared__ __attribute__((aligned(16))) char smb[];
-    const int64_t chunk = blockIdx.y;
-    const int k0 = blockIdx.x * C::CPW;
-    const int nk = a.K - k0 < C::CPW ? a.K - k0 : C::CPW;
-    const int64_t c0 = chunk * a.rows_per_chunk;
-    int64_t c1 = c0 + a.rows_per_chunk;
-    if (c1 > a.V) c1 = a.V;
-    const int nb = c1 > c0 ? (int)((c1 - c0 + C::RB - 1) / C::RB) : 0;
+    const CovChunk ch = cov_chunk<C::CPW, C::RB>(a);
     const int tid = threadIdx.x, wid = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    if (wid & 1) covfb3_body<D, 1>(a, smb, nb, k0, nk, c0, c1, chunk, wid, lane);
-    else covfb3_body<D, 0>(a, smb, nb, k0, nk, c0, c1, chunk, wid, lane);
+    if (wid & 1) covfb3_body<D, 1>(a, smb, ch, wid, lane);
+    else covfb3_body<D, 0>(a, smb, ch, wid, lane);
 }
 
 // Any d <= 128 on the VALU: thread owns entries tid + 256 q of the d x d output.
@@ -828,10 +826,9 @@ __global__ void __launch_bounds__(256) k_gmm_cov_valu(CovArgs a) {
     constexpr int MAXQ = 64;  // 128 * 128 / 256
     __shared__ float xs[kCovRB * 129];
     __shared__ float ws[kCovRB];
-    const int d = a.d, k = blockIdx.x, tid = threadIdx.x;
-    const int64_t c0 = (int64_t)blockIdx.y * a.rows_per_chunk;
-    int64_t c1 = c0 + a.rows_per_chunk;
-    if (c1 > a.V) c1 = a.V;
+    const CovChunk ch = cov_chunk<1, kCovRB>(a);
+    const int d = a.d, k = ch.k0, tid = threadIdx.x;
+    const int64_t c0 = ch.c0, c1 = ch.c1;
     const int ne = d * d;
     float acc[MAXQ];
 #pragma unroll
@@ -855,7 +852,7 @@ __global__ void __launch_bounds__(256) k_gmm_cov_valu(CovArgs a) {
             }
         }
     }
-    float *out = a.out + ((int64_t)blockIdx.y * a.K + k) * ne;
+    float *out = a.out + ch.part(a, 0) * ne;
 #pragma unroll
     for (int q = 0; q < MAXQ; ++q) {
         const int e = tid + 256 * q;
@@ -874,9 +871,8 @@ __global__ void __launch_bounds__(kThreads) k_gmm_cov_wide(CovArgs a) {
     const int ti = blockIdx.z / nt, tj = blockIdx.z % nt;
     float *xs = smem;                 // [kCovWideRB][d]
     float *ws = xs + kCovWideRB * d;  // [kCovWideRB]
-    const int64_t c0 = (int64_t)blockIdx.y * a.rows_per_chunk;
-    int64_t c1 = c0 + a.rows_per_chunk;
-    if (c1 > a.V) c1 = a.V;
+    const CovChunk ch = cov_chunk<1, kCovWideRB>(a);
+    const int64_t c0 = ch.c0, c1 = ch.c1;
     float acc[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
@@ -900,7 +896,7 @@ __global__ void __launch_bounds__(kThreads) k_gmm_cov_wide(CovArgs a) {
             }
         }
     }
-    float *out = a.out + ((int64_t)blockIdx.y * a.K + k) * d * d;
+    float *out = a.out + ch.part(a, 0) * d * d;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         const int e = tid + 256 * q;
@@ -909,30 +905,33 @@ __global__ void __launch_bounds__(kThreads) k_gmm_cov_wide(CovArgs a) {
     }
 }
 
-// out[i] = sum_c part[c][i] in chunk order (deterministic), i over K d^2 entries.  Four entries
-// per thread (16-byte loads when n % 4 == 0) and eight chunks' loads issued ahead of their adds,
-// which stay in chunk order: 534 MB of partials at C4 in 0.17 ms as one dword and one chunk at a
-// time per thread.
+// sum_c p[c stride] over the chunks, added strictly in chunk order from 0 (deterministic); eight
+// chunks' loads are issued ahead of their adds.
+__device__ __forceinline__ f32x4 cov_chunk_sum(const f32x4 *p, int64_t stride, int chunks) {
+    f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
+    int c = 0;
+    for (; c + 8 <= chunks; c += 8) {
+        f32x4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(c + u) * stride];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; c < chunks; ++c) s += p[(int64_t)c * stride];
+    return s;
+}
+
+// out[i] = sum_c part[c][i] in chunk order, i over K d^2 entries.  Four entries per thread
+// (16-byte loads, cov_chunk_sum, when n % 4 == 0): 534 MB of partials at C4 in 0.17 ms as one dword
+// and one chunk at a time per thread.
 template <bool VEC4>
 __global__ void __launch_bounds__(256) k_gmm_cov_reduce(const float *part, float *out, int64_t n,
                                                         int chunks) {
-    using f32x4 = __attribute__((ext_vector_type(4))) float;
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;  // entries 4 q .. 4 q + 3
     if (4 * q >= n) return;
     if (VEC4) {
-        const f32x4 *p = reinterpret_cast<const f32x4 *>(part) + q;
-        const int64_t stride = n / 4;
-        f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-        int c = 0;
-        for (; c + 8 <= chunks; c += 8) {
-            f32x4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(c + u) * stride];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += v[u];
-        }
-        for (; c < chunks; ++c) s += p[(int64_t)c * stride];
-        reinterpret_cast<f32x4 *>(out)[q] = s;
+        reinterpret_cast<f32x4 *>(out)[q] =
+            cov_chunk_sum(reinterpret_cast<const f32x4 *>(part) + q, n / 4, chunks);
     } else {
         for (int64_t i = 4 * q; i < 4 * q + 4 && i < n; ++i) {
             float s = 0.0f;
@@ -945,12 +944,11 @@ __global__ void __launch_bounds__(256) k_gmm_cov_reduce(const float *part, float
 // The 32-wide-tile kernels' partials hold only the upper tiles (CovArgs::upper_only): the threads
 // cover the upper tiles only -- thread q of component k takes upper tile t = (q / 256) % NTU
 // (row-major order of the upper triangle), row r = (q % 256) / 8 and columns 4 g .. 4 g + 3
-// (g = q % 8) of it, eight lanes per 128-byte tile row -- sums them over the chunks (16-byte loads,
-// eight chunks in flight, in chunk order) and writes them and their mirror images.
+// (g = q % 8) of it, eight lanes per 128-byte tile row -- sums them over the chunks
+// (cov_chunk_sum) and writes them and their mirror images.
 template <int D>
 __global__ void __launch_bounds__(256) k_gmm_cov_reduce_upper(const float *part, float *out,
                                                                 int64_t n, int chunks, int K) {
-    using f32x4 = __attribute__((ext_vector_type(4))) float;
     constexpr int NT = D / 32, NTU = NT * (NT + 1) / 2;
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= (int64_t)K * NTU * 256) return;
@@ -962,18 +960,7 @@ __global__ void __launch_bounds__(256) k_gmm_cov_reduce_upper(const float *part,
     }
     const int tj = ti + t, i = 32 * ti + w / 8, j = 32 * tj + 4 * (w % 8);
     const int64_t e = (int64_t)k * D * D + (int64_t)i * D + j;
-    const f32x4 *p = reinterpret_cast<const f32x4 *>(part + e);
-    const int64_t stride = n / 4;
-    f32x4 s = {0.0f, 0.0f, 0.0f, 0.0f};
-    int c = 0;
-    for (; c + 8 <= chunks; c += 8) {
-        f32x4 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = p[(int64_t)(c + u) * stride];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; c < chunks; ++c) s += p[(int64_t)c * stride];
+    const f32x4 s = cov_chunk_sum(reinterpret_cast<const f32x4 *>(part + e), n / 4, chunks);
     *reinterpret_cast<f32x4 *>(out + e) = s;
     if (tj > ti) {
         float *m = out + (int64_t)k * D * D + (int64_t)j * D + i;  // (j, i)
@@ -981,6 +968,9 @@ __global__ void __launch_bounds__(256) k_gmm_cov_reduce_upper(const float *part,
         for (int u = 0; u < 4; ++u) m[(int64_t)u * D] = s[u];
     }
 }
+
+// the reducers' launch signature: (dev, part, out, n = K d^2 entries per chunk, chunks, stream)
+using CovReduce = int (*)(int, const float *, float *, int64_t, int, void *);
 
 static int launch_cov_reduce(int dev, const float *part, float *out, int64_t n, int chunks,
                              void *stream) {
@@ -998,276 +988,16 @@ static int launch_cov_reduce_upper(int dev, const float *part, float *out, int64
                   part, out, n, chunks, K);
 }
 
-// ---- M-step parameters + E-step constants (come_gmm_params) ----------------------------------
-//
-// One workgroup per component, float64 in LDS (d <= 128: 128 x 129 doubles = 129 KB): cov =
-// S / nk + reg I (sklearn _estimate_gaussian_covariances_full), the right-looking Cholesky
-// factorisation in place (U = L^T in the upper triangle), then prec_chol = L^-T = U^-1 bottom-up by
-// rows with two lanes of one wavefront per column (sklearn _compute_precision_cholesky:
-// solve_triangular(L, I).T): a column's values are written and read by its own wavefront only, so
-// the inverse needs no barrier.  Then the E-step's fp32 inputs.  Replaces ~30 small launches (torch
-// cholesky_ex / solve_triangular / einsum) and a host sync per EM iteration.
-struct ParamsArgs {
-    const double *__restrict__ S, *__restrict__ nk, *__restrict__ means, *__restrict__ weights;
-    int K, d;
-    double reg;
-    double *cov, *pc;
-    float *e_pc, *e_mp, *e_ln;
-    int *info;
-};
-
-// Right-looking Cholesky steps j .. j + NB - 1 in one phase (no barrier inside).  Step m turns
-// A^(m) into A^(m+1)[i][c] = A^(m)[i][c] - t_m(i) A^(m)[c][j + m], t_m(i) = A^(m)[i][j + m] / pivot_m.
-// Each thread recomputes, in registers and in exactly that order, the panel values A^(m)[i][j + m]
-// it needs (the same expressions as one step per barrier, so the factor is bit-identical), writes
-// rows j + m of U = L^T to the upper triangle and the NB steps' trailing update to the lower --
-// disjoint from every read of the phase.
-template <int NB>
-__device__ __forceinline__ void chol_panel(double *A, int LD, int d, int j, int tid, double *ld,
-                                           int *bad) {
-    const int tx = tid & 15, ty = tid >> 4;
-    double P[NB][NB], ra[NB], lk[NB];  // P[k][m] = A^(m)[j + k][j + m], m < k
-    bool okv[NB];
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-        double t[NB];
-#pragma unroll
-        for (int m = 0; m <= k; ++m) {
-            double x = A[(j + k) * LD + j + m];
-#pragma unroll
-            for (int q = 0; q < m; ++q) x = x - t[q] * P[m][q];
-            if (m < k) {
-                P[k][m] = x;
-                t[m] = x * ra[m];
-            } else {
-                okv[k] = x > 0.0;
-                lk[k] = sqrt(okv[k] ? x : 1.0);
-                ra[k] = 1.0 / (okv[k] ? x : 1.0);
-            }
-        }
-    }
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < NB; ++k) {
-            ld[j + k] = lk[k];
-            if (!okv[k] && *bad == 0) *bad = j + k + 1;
-        }
-    }
-    // U rows j + m: U[j + m][i] = A^(m)[i][j + m] / L[j + m][j + m] for i > j + m
-    for (int i = j + 1 + tid; i < d; i += 256) {
-        double t[NB];
-#pragma unroll
-        for (int m = 0; m < NB; ++m) {
-            if (j + m >= i) break;
-            double x = A[i * LD + j + m];
-#pragma unroll
-            for (int q = 0; q < m; ++q) x = x - t[q] * P[m][q];
-            t[m] = x * ra[m];
-            A[(j + m) * LD + i] = x / lk[m];
-        }
-    }
-    // trailing rows / columns from j + NB: the thread's columns cc = j + NB + tx + 16 n with their
-    // panel values in registers, then each row's elements loaded, updated by the NB steps, stored
-    double c[NB][8];
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-        const int cc = j + NB + tx + 16 * n;
-        double t[NB];
-#pragma unroll
-        for (int m = 0; m < NB; ++m) {
-            double x = cc < d ? A[cc * LD + j + m] : 0.0;
-#pragma unroll
-            for (int q = 0; q < m; ++q) x = x - t[q] * P[m][q];
-            t[m] = x * ra[m];
-            c[m][n] = x;
-        }
-    }
-    for (int ii = j + NB + ty; ii < d; ii += 16) {
-        double t[NB];
-#pragma unroll
-        for (int m = 0; m < NB; ++m) {
-            double x = A[ii * LD + j + m];
-#pragma unroll
-            for (int q = 0; q < m; ++q) x = x - t[q] * P[m][q];
-            t[m] = x * ra[m];
-        }
-        double v[8];
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            const int cc = j + NB + tx + 16 * n;
-            v[n] = cc <= ii ? A[ii * LD + cc] : 0.0;
-        }
-#pragma unroll
-        for (int n = 0; n < 8; ++n) {
-            const int cc = j + NB + tx + 16 * n;
-            double y = v[n];
-#pragma unroll
-            for (int m = 0; m < NB; ++m) y = y - t[m] * c[m][n];
-            if (cc <= ii) A[ii * LD + cc] = y;
-        }
-    }
-}
-
-// Rows r, r - 1, .., r - R + 1 of P = U^-1 for the lane pair of column c (h: the parity of q it
-// sums): the R dots over q > r share the loads of P[q][c]; then row r - k adds U[r - k][q] P[q][c]
-// for q = r, r - 1, .., r - k + 1 from registers before its dot.  P[q][c] (q < c) sits at A[c][q],
-// the diagonal in pd.  Written by the h = 0 lane; read back only by this wavefront.
-template <int R>
-__device__ __forceinline__ void inv_rows(double *A, int LD, int d, int r, int c, int h,
-                                         double pdc, const double *pd) {
-    double S[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) S[k] = 0.0;
-    if (c < d && c > r) {
-        double s[R][4];
-#pragma unroll
-        for (int k = 0; k < R; ++k) s[k][0] = s[k][1] = s[k][2] = s[k][3] = 0.0;
-        int q = r + 1 + h;
-        for (; q + 6 < c; q += 8) {
-            const double p0 = A[c * LD + q], p1 = A[c * LD + q + 2];
-            const double p2 = A[c * LD + q + 4], p3 = A[c * LD + q + 6];
-#pragma unroll
-            for (int k = 0; k < R; ++k) {
-                const double *u = A + (r - k) * LD + q;
-                s[k][0] += u[0] * p0;
-                s[k][1] += u[2] * p1;
-                s[k][2] += u[4] * p2;
-                s[k][3] += u[6] * p3;
-            }
-        }
-        for (; q <= c; q += 2) {
-            const double pq = q == c ? pdc : A[c * LD + q];
-#pragma unroll
-            for (int k = 0; k < R; ++k) s[k][0] += A[(r - k) * LD + q] * pq;
-        }
-#pragma unroll
-        for (int k = 0; k < R; ++k) S[k] = (s[k][0] + s[k][1]) + (s[k][2] + s[k][3]);
-    }
-    double O[R];
-#pragma unroll
-    for (int k = 0; k < R; ++k) O[k] = __shfl_xor(S[k], 1);
-    if (h == 0 && c < d && c >= r - R + 1) {
-        double Pv[R];  // P[r - k][c]
-#pragma unroll
-        for (int k = 0; k < R; ++k) {
-            const int rk = r - k;
-            if (c <= rk) {
-                Pv[k] = c == rk ? pd[rk] : 0.0;
-                continue;
-            }
-            double acc;
-            if (k == 0) {
-                acc = S[0] + O[0];
-            } else {
-                acc = A[rk * LD + r] * Pv[0];
-#pragma unroll
-                for (int m = 1; m < k; ++m) acc = acc + A[rk * LD + r - m] * Pv[m];
-                acc = acc + (S[k] + O[k]);
-            }
-            Pv[k] = -acc * pd[rk];
-            A[c * LD + rk] = Pv[k];
-        }
-    }
-}
-
-// Cholesky columns per barrier and inverse rows per round (scripts/params_ab.py at K = 50, d = 128:
-// 8 / 4 -> 0.190 ms, 4 / 4 0.198, 8 / 2 0.215, 4 / 2 0.223; profiles/r07_ab_gmm_params6.txt)
-constexpr int kParamsNB = 8, kParamsInvR = 4;
-
-__global__ void __launch_bounds__(256) k_gmm_params(ParamsArgs p) {
-    extern __shared__ __attribute__((aligned(16))) double A[];  // [d][d + 1]
-    __shared__ double ld[128], pd[128], mus[128], red[256];
-    __shared__ int bad;
-    const int k = blockIdx.x, d = p.d, LD = d + 1, tid = threadIdx.x, dd = d * d;
-    const int tx = tid & 15, ty = tid >> 4;
-    const double *__restrict__ S = p.S + (int64_t)k * dd;
-    double *__restrict__ cov = p.cov + (int64_t)k * dd;
-    const double nkk = p.nk[k];
-    // S / nk[:, None, None] + reg I (the torch path's order), 16 coalesced loads in flight per lane
-    for (int base = tid; base < dd; base += 256 * 16) {
-        double v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = base + 256 * u < dd ? S[base + 256 * u] : 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int e = base + 256 * u;
-            if (e >= dd) break;
-            const int i = e / d, j = e - i * d;
-            const double c = i == j ? v[u] / nkk + p.reg : v[u] / nkk;
-            cov[e] = c;
-            A[i * LD + j] = c;
-        }
-    }
-    if (tid < d) mus[tid] = p.means[(int64_t)k * d + tid];
-    if (tid == 0) bad = 0;
-    __syncthreads();
-    // Cholesky, right-looking, four columns per barrier (chol_panel)
-    int j = 0;
-    for (; j + kParamsNB <= d; j += kParamsNB) {
-        chol_panel<kParamsNB>(A, LD, d, j, tid, ld, &bad);
-        __syncthreads();
-    }
-    if (kParamsNB > 4 && j + 4 <= d) {
-        chol_panel<4>(A, LD, d, j, tid, ld, &bad);
-        __syncthreads();
-        j += 4;
-    }
-    if (j + 2 <= d) {
-        chol_panel<2>(A, LD, d, j, tid, ld, &bad);
-        __syncthreads();
-        j += 2;
-    }
-    if (j < d) {
-        chol_panel<1>(A, LD, d, j, tid, ld, &bad);
-        __syncthreads();
-    }
-    // P = U^-1 = L^-T (upper), bottom-up by rows: P[r][c] = -(sum_{r<q<=c} U[r][q] P[q][c]) /
-    // U[r][r]; P[q][c] (q < c) kept in the lower triangle at A[c][q], its diagonal in pd.  Column
-    // c = tid / 2 belongs to lanes 2c, 2c + 1 of one wavefront, which split the dot by the parity
-    // of q (four partial sums each) and combine by a lane exchange: every P value a lane reads was
-    // written by its own wavefront at an earlier row (LDS accesses of a wavefront are ordered), so
-    // the rows need no barrier.
-    for (int r = tid; r < d; r += 256) pd[r] = 1.0 / ld[r];
-    __syncthreads();
-    {
-        const int c = tid >> 1, h = tid & 1;
-        const double pdc = c < d ? pd[c] : 0.0;
-        int r = d - 2;
-        for (; r >= kParamsInvR - 1; r -= kParamsInvR)
-            inv_rows<kParamsInvR>(A, LD, d, r, c, h, pdc, pd);
-        if (kParamsInvR > 2 && r >= 1) {
-            inv_rows<2>(A, LD, d, r, c, h, pdc, pd);
-            r -= 2;
-        }
-        if (r == 0) inv_rows<1>(A, LD, d, r, c, h, pdc, pd);
-    }
-    __syncthreads();
-    // prec_chol (upper): row r, column c > r at A[c][r], pd on the diagonal
-    double *pc = p.pc + (int64_t)k * d * d;
-    float *epc = p.e_pc + (int64_t)k * d * d;
-    for (int r = ty; r < d; r += 16)
-        for (int c = tx; c < d; c += 16) {
-            const double v = c < r ? 0.0 : (c == r ? pd[r] : A[c * LD + r]);
-            pc[r * d + c] = v;
-            epc[r * d + c] = (float)v;
-        }
-    // mu_k prec_chol_k (column j: rows i <= j) and log det = sum log diag(prec_chol)
-    if (tid < d) {
-        const int j = tid;
-        double s = mus[j] * pd[j];
-        for (int i = 0; i < j; ++i) s += mus[i] * A[j * LD + i];
-        p.e_mp[(int64_t)k * d + j] = (float)s;
-    }
-    red[tid] = tid < d ? log(pd[tid]) : 0.0;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        p.e_ln[k] = (float)(log(p.weights[k]) + red[0] - 0.5 * d * log(2.0 * 3.14159265358979323846));
-        p.info[k] = bad;
-    }
+// The scatter kernel of a call.  cv = gmm_cov_async: 4 (default) = k_gmm_cov_fb3 at d = 128 /
+// k_gmm_cov_bf3 at d = 64 (bf16 parts), 5 = k_gmm_cov_bf3, 3 = k_gmm_cov16 (fp32 16x16x4).  x16: x
+// is 16-byte aligned (the MFMA kernels' loads).  fb3_fits: a chunk of x and of resp is under 2 GB
+// each (k_gmm_cov_fb3's buffer descriptors span one).
+enum class CovForm { Wide, Valu, Cov16, Bf3, Fb3 };
+static CovForm cov_form(int d, bool x16, int cv, bool fb3_fits) {
+    if (d > 128) return CovForm::Wide;
+    if ((d != 64 && d != 128) || !x16) return CovForm::Valu;
+    if (cv == 3) return CovForm::Cov16;
+    return cv == 4 && d == 128 && fb3_fits ? CovForm::Fb3 : CovForm::Bf3;
 }
 
 }  // namespace come
@@ -1283,83 +1013,50 @@ extern "C" int come_gmm_scatter(const float *x, int64_t V, int d, const float *r
     if (!x || !resp || !means || !scatter_out || (chunks > 1 && !scratch))
         return set_error(COME_E_INVALID, "null pointer");
     int dev;
-    int rc = ensure_init(&dev);
+    const int rc = ensure_init(&dev);
     if (rc) return rc;
+    const int cv = current_opts().gmm_cov_async;
+    if (d <= 128 && (cv < 3 || cv > 5))  // (the wide kernel has one form: the option is not read)
+        return set_error(COME_E_INVALID, "gmm_cov_async must be 3, 4 or 5 (got %d)", cv);
     const int64_t n = (int64_t)K * d * d;
     int64_t per = (V + chunks - 1) / chunks;
-    per = (per + kCovRB - 1) / kCovRB * kCovRB;
-    if (per < kCovRB) per = kCovRB;
+    per = std::max<int64_t>(kCovRB, (per + kCovRB - 1) / kCovRB * kCovRB);
     const int used = V == 0 ? 1 : (int)((V + per - 1) / per);
-    CovArgs a{x, resp, means, used > 1 ? scratch : scatter_out, V, per, d, K, 0};
-    const bool mfma = (d == 64 || d == 128) && ((uintptr_t)x % 16) == 0;
-    if (d > 128) {
-        const int nt = (d + 63) / 64;
-        rc = launch(dev, k_gmm_cov_wide, "k_gmm_cov_wide launch", dim3(K, used, nt * nt),
-                    dim3(kThreads), {sizeof(float) * ((size_t)kCovWideRB * d + kCovWideRB)}, stream,
-                    a);
-        if (rc || used == 1) return rc;
-        return launch_cov_reduce(dev, scratch, scatter_out, n, used, stream);
-    }
-    // gmm_cov_async: 4 (default) = k_gmm_cov_fb3 at d = 128 / k_gmm_cov_bf3 at d = 64 (bf16 parts),
-    // 5 = k_gmm_cov_bf3 at both widths, 3 = k_gmm_cov16 (fp32 16x16x4)
-    const int cv = current_opts().gmm_cov_async;
-    if (cv < 3 || cv > 5)
-        return set_error(COME_E_INVALID, "gmm_cov_async must be 3, 4 or 5 (got %d)", cv);
-    if (!mfma) {
-        rc = launch(dev, k_gmm_cov_valu, "k_gmm_cov launch", dim3(K, used), dim3(256), {0}, stream,
-                    a);
-        if (rc || used == 1) return rc;
-        return launch_cov_reduce(dev, scratch, scatter_out, n, used, stream);
-    }
-    // 4 at d = 128: k_gmm_cov_fb3 (its buffer descriptors span one chunk of x and of resp: each
-    // under 2 GB, else k_gmm_cov_bf3); 4 at d = 64, and 5: k_gmm_cov_bf3
     const bool fb3_fits = per * std::max(d, K) * (int64_t)sizeof(float) < (int64_t(1) << 31);
-    if (cv == 4 && d == 128 && fb3_fits) {
+    const CovForm form = cov_form(d, (uintptr_t)x % 16 == 0, cv, fb3_fits);
+    const bool tiles32 = form == CovForm::Bf3 || form == CovForm::Fb3;
+    const CovArgs a{x, resp, means, used > 1 ? scratch : scatter_out, V, per, d, K,
+                    tiles32 && used > 1};
+    // the scatter kernel on (gx, used, gz) workgroups, then the reduction of more than one chunk
+    auto run = [&](auto kern, const char *what, int gx, int gz, int threads, Lds lds,
+                   CovReduce reduce) {
+        const int rc = launch(dev, kern, what, dim3(gx, used, gz), dim3(threads), lds, stream, a);
+        if (rc || used == 1) return rc;
+        return reduce(dev, scratch, scatter_out, n, used, stream);
+    };
+    const int nt = (d + 63) / 64;  // (k_gmm_cov_wide: one workgroup per 64 x 64 output tile)
+    switch (form) {
+    case CovForm::Wide:
+        return run(k_gmm_cov_wide, "k_gmm_cov_wide launch", K, nt * nt, kThreads,
+                   {sizeof(float) * ((size_t)kCovWideRB * d + kCovWideRB)}, launch_cov_reduce);
+    case CovForm::Valu:
+        return run(k_gmm_cov_valu, "k_gmm_cov launch", K, 1, 256, {0}, launch_cov_reduce);
+    case CovForm::Fb3: {
         using C = CovFb3<128>;
-        a.upper_only = used > 1;
-        rc = launch(dev, k_gmm_cov_fb3<128>, "k_gmm_cov_fb3 launch",
-                    dim3((K + C::CPW - 1) / C::CPW, used), dim3(C::THREADS), {C::LDS_BYTES}, stream,
-                    a);
-        if (rc || used == 1) return rc;
-        return launch_cov_reduce_upper<128>(dev, scratch, scatter_out, n, used, stream);
+        return run(k_gmm_cov_fb3<128>, "k_gmm_cov_fb3 launch", (K + C::CPW - 1) / C::CPW, 1,
+                   C::THREADS, {C::LDS_BYTES}, launch_cov_reduce_upper<128>);
     }
-    return with_width(d, [&](auto width) {
-        constexpr int D = decltype(width)::value;
-        if (cv == 3) {
-            using C = Cov16<D>;
-            const int rc = launch(dev, k_gmm_cov16<D>, "k_gmm_cov launch",
-                                  dim3((K + C::CPW - 1) / C::CPW, used), dim3(C::THREADS), {0},
-                                  stream, a);
-            if (rc || used == 1) return rc;
-            return launch_cov_reduce(dev, scratch, scatter_out, n, used, stream);
-        }
-        using C = CovBf3<D>;
-        a.upper_only = used > 1;
-        const int rc = launch(dev, k_gmm_cov_bf3<D>, "k_gmm_cov_bf3 launch",
-                              dim3((K + C::CPW - 1) / C::CPW, used), dim3(C::THREADS),
-                              {C::LDS_BYTES}, stream, a);
-        if (rc || used == 1) return rc;
-        return launch_cov_reduce_upper<D>(dev, scratch, scatter_out, n, used, stream);
-    });
-}
-
-extern "C" int come_gmm_params(const double *scatter, const double *nk, const double *means,
-                               const double *weights, int K, int d, double reg_covar,
-                               double *cov_out, double *prec_chol_out, float *e_prec_chol,
-                               float *e_mu_prec, float *e_log_norm, int *info, void *stream) {
-    if (K < 1 || d < 1 || d > 128)
-        return set_error(COME_E_INVALID, "gmm_params: need K >= 1 and 1 <= d <= 128");
-    if (!scatter || !nk || !means || !weights || !cov_out || !prec_chol_out || !e_prec_chol ||
-        !e_mu_prec || !e_log_norm || !info)
-        return set_error(COME_E_INVALID, "null pointer");
-    int dev;
-    int rc = ensure_init(&dev);
-    if (rc) return rc;
-    ParamsArgs p{scatter, nk, means, weights, K, d, reg_covar, cov_out, prec_chol_out,
-                 e_prec_chol, e_mu_prec, e_log_norm, info};
-    // (the kernel's static LDS, ~3 KB, counts against the 160 KB too: the limit asked for is what
-    // d = 128 needs, 129 KB, not the whole of it)
-    return launch(dev, k_gmm_params, "k_gmm_params launch", dim3(K), dim3(256),
-                  {sizeof(double) * (size_t)d * (d + 1), (int)(sizeof(double) * 128 * 129)}, stream,
-                  p);
+    default:
+        return with_width(d, [&](auto width) {
+            constexpr int D = decltype(width)::value;
+            if (form == CovForm::Cov16) {
+                using C = Cov16<D>;
+                return run(k_gmm_cov16<D>, "k_gmm_cov launch", (K + C::CPW - 1) / C::CPW, 1,
+                           C::THREADS, {0}, launch_cov_reduce);
+            }
+            using C = CovBf3<D>;
+            return run(k_gmm_cov_bf3<D>, "k_gmm_cov_bf3 launch", (K + C::CPW - 1) / C::CPW, 1,
+                       C::THREADS, {C::LDS_BYTES}, launch_cov_reduce_upper<D>);
+        });
+    }
 }

@@ -325,6 +325,34 @@ def test_scatter_default_and_fallback_agree(V, K, d, chunks):
         np.testing.assert_allclose(o, np.swapaxes(o, 1, 2), rtol=0, atol=1e-6 * np.abs(o).max())
 
 
+@pytest.mark.parametrize("d,cov", [(128, 3), (128, 4), (128, 5), (64, 3), (64, 4), (5, None),
+                                   (129, None)])
+def test_scatter_chunks_fold_in_order(d, cov):
+    """The chunked scatter is the fp32 left fold, in chunk order and from 0, of its chunks' own
+    scatters, bit for bit: V = 699 rows with chunks = 11 are 11 used chunks of 64 rows (the last
+    holds 59: eight chunks loaded ahead, then a tail of three), and chunk c alone is the one-chunk
+    call on rows 64 c .. 64 c + 63 (a slice starts on a 16-byte boundary, its workgroups run the
+    same blocks in the same order, and the reducers' mirrored entries are copies of their upper
+    twins).  Every scatter kernel and every reducer: k_gmm_cov16 (3), k_gmm_cov_fb3 /
+    k_gmm_cov_bf3 (4, 5) with k_gmm_cov_reduce_upper, k_gmm_cov_valu at d = 5 (K d^2 = 75:
+    k_gmm_cov_reduce<false>), k_gmm_cov_wide at d = 129 (K d^2 % 4 = 3)."""
+    V, K, chunks, R = 699, 3, 11, 64
+    rng = np.random.RandomState(d)
+    t = lambda a: torch.as_tensor(a, device=dev())  # noqa: E731
+    X = t(rng.standard_normal((V, d)).astype(np.float32))
+    resp = t(rng.dirichlet(np.ones(K), V).astype(np.float32))
+    M = t(rng.standard_normal((K, d)).astype(np.float32))
+    with options(**({"gmm_cov_async": cov} if cov else {})):
+        whole = gmm.scatter(X, resp, M, chunks=chunks).cpu().numpy()
+        fold = np.zeros((K, d, d), np.float32)
+        for c in range(chunks):
+            xs, rs = X[R * c:R * c + R], resp[R * c:R * c + R]
+            assert xs.data_ptr() % 16 == 0 and len(xs) == (R if c < chunks - 1 else 59)
+            fold = fold + gmm.scatter(xs, rs, M, chunks=1).cpu().numpy()
+    assert fold.dtype == np.float32 and np.isfinite(whole).all()
+    assert np.array_equal(whole, fold)
+
+
 def test_community2vec_trains_at_d256():
     """A model with layer1_size = 256 (the SGNS kernels' C5 width) goes through the whole
     community phase: GPU GMM fit, responsibilities, community step (wide VALU kernels); the
