@@ -40,6 +40,11 @@
                   in the same run, bit-identity of every diagonal entry across two passes, and each
                   kernel's roofline: the larger of its compulsory bytes over HBM and its fused
                   multiply-adds over the fp32 vector peak.
+  --workload topk  exact top-10 cosine neighbour search over a 1M x 128 table (come_topk through
+                  neighbors.Index.search) at Q = 16,384 and Q = 1, beside the torch chain it
+                  replaces (normalised matmul + torch.topk over query batches of 2,048) timed in the
+                  same run: ms, queries/s, executed flops over the fp32 MFMA peak, and each path's
+                  peak device memory over the tables.
 Each prints one JSON line.  CPU baselines on a bounded sample: O1 the builder's Hogwild C
 restatement of train_o1 (oracle/come_oracle_mt.c; reported beside it as the reference-equivalent
 rate, restatement / its calibrated speed-up over the reference's GIL-bound Node2Vec.train,
@@ -827,6 +832,77 @@ def c4_diag_bench(args):
         "shapes": shapes, "cpu_baseline": None}))
 
 
+def topk_bench(args):
+    """Exact top-k neighbour search (come_topk) beside the torch chain it replaces, V rows of d
+    floats, k = 10, cosine, at Q = 16,384 and at Q = 1; both paths get the base norms / the
+    normalised base computed once, outside the timing."""
+    import torch
+    from come_amd import neighbors
+    dev = torch.device("cuda", 0)
+    V, d, k, QB = args.nodes, args.dim, 10, 2048
+    g = torch.Generator(device=dev).manual_seed(17)
+    base = torch.randn((V, d), generator=g, device=dev, dtype=torch.float32)
+    index = neighbors.Index(base, "cosine")
+    base_n = torch.nn.functional.normalize(base, dim=1)
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    torch.cuda.synchronize()
+    rows = []
+    for Q in (16384, 1):
+        qs = torch.randn((Q, d), generator=g, device=dev, dtype=torch.float32)
+
+        def fused():
+            return index.search(qs, k)
+
+        def chain():
+            out = []
+            for r0 in range(0, Q, QB):
+                qn = torch.nn.functional.normalize(qs[r0:r0 + QB], dim=1)
+                sc, ix = torch.topk(qn @ base_n.t(), k, dim=1)
+                out.append((ix, sc))
+            return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out])
+
+        res = {}
+        for name, fn, steps, warm in (("fused", fused, args.steps, args.warmup),
+                                      ("torch_chain", chain, min(args.steps, 3), 1),
+                                      ("fused_again", fused, args.steps, 1)):
+            torch.cuda.synchronize()
+            held = torch.cuda.memory_allocated(dev)
+            torch.cuda.reset_peak_memory_stats(dev)
+            _, ks = timed(fn, steps, warm)
+            ms = float(np.mean(ks))
+            res[name] = {"ms": ms, "ms_min": float(np.min(ks)), "ms_max": float(np.max(ks)),
+                         "steps": steps, "queries_per_s": Q / (ms / 1e3),
+                         "tflops": 2.0 * Q * V * d / (ms / 1e3) / 1e12,
+                         "peak_bytes_over_the_tables":
+                             int(torch.cuda.max_memory_allocated(dev) - held)}
+        # executed flops of the fused kernel: whole 128-query tiles x whole 32-row base tiles
+        chunks, per = neighbors.plan(Q, V, d, k, cus)
+        executed = 2.0 * (-(-Q // 128) * 128) * (chunks * per) * d
+        for name in ("fused", "fused_again"):
+            res[name]["executed_tflops"] = executed / (res[name]["ms"] / 1e3) / 1e12
+            res[name]["frac_of_f32_mfma_peak"] = res[name]["executed_tflops"] / F32_MFMA_PEAK_TFLOPS
+        (fi, fs), (ti, ts) = fused(), chain()
+        same = float((fi == ti).float().mean())
+        rows.append({"Q": Q, "chunks": chunks, "rows_per_chunk": per,
+                     "scratch_bytes": neighbors.scratch_bytes(Q, V, k, chunks, True),
+                     "index_agreement_with_torch": same,
+                     "max_abs_score_difference": float((fs - ts).abs().max()), **res})
+        log("Q=%d: fused %.3f ms, torch chain %.3f ms, fused again %.3f ms" % (
+            Q, res["fused"]["ms"], res["torch_chain"]["ms"], res["fused_again"]["ms"]))
+    big = rows[0]
+    print(json.dumps({
+        "metric": "exact top-%d cosine search, ms per %d queries, V=%d d=%d" % (k, big["Q"], V, d),
+        "value": big["fused"]["ms"], "unit": "ms", "n_gpus": 1, "steps": args.steps,
+        "warmup": args.warmup, "higher_is_better": False, "dtype": "f32 (fp32 MFMA)",
+        "data": "synthetic N(0, 1) rows (device generator, seed 17)",
+        "config": {"workload": "come_topk (neighbors.Index.search) beside normalised matmul + "
+                               "torch.topk over query batches of %d" % QB},
+        "roofline": {"bound": "mfma", "achieved": big["fused"]["executed_tflops"],
+                     "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s (executed)",
+                     "frac": big["fused"]["frac_of_f32_mfma_peak"]},
+        "shapes": rows}))
+
+
 def blas_threads():
     """Threads of the BLAS pool numpy / scipy / sklearn run on in this process (threadpoolctl),
     None if it cannot tell."""
@@ -840,7 +916,7 @@ def blas_threads():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", choices=["c2", "c4", "walks", "kmeans", "community_loss", "sgns_loss", "c4_diag"], required=True)
+    ap.add_argument("--workload", choices=["c2", "c4", "walks", "kmeans", "community_loss", "sgns_loss", "c4_diag", "topk"], required=True)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--dim", type=int, default=128)
@@ -871,7 +947,7 @@ def main():
             _lib.set_option(k, int(v))
     {"c2": c2, "c4": c4, "walks": walks, "kmeans": kmeans_bench,
      "community_loss": community_loss_bench, "sgns_loss": sgns_loss_bench,
-     "c4_diag": c4_diag_bench}[args.workload](args)
+     "c4_diag": c4_diag_bench, "topk": topk_bench}[args.workload](args)
 
 
 if __name__ == "__main__":

@@ -17,6 +17,8 @@ search path there.  Module map, mirroring the reference layout:
     come_amd.kmeans               <- (new) k-means on the GPU: the mixture's initialisation
                                      (kmeans_backend='native', kmeans_seeding='native') and a
                                      KMeans estimator
+    come_amd.neighbors            <- (new) exact top-k neighbour search over the embedding
+                                     tables (most_similar, k-NN graph), no Q x V score matrix
     come_amd.io_utils             <- utils/IO_utils.py (labels / embedding text formats)
     come_amd.graph                <- synthetic graphs + random walks (inputs of the hot path)
     come_amd.distributed          <- (new) walk sharding + delta all-reduce over RCCL

@@ -38,6 +38,8 @@ extern "C" {
  * ABI 5, additive: come_edge_cdf, come_edge_sample, their CPU twins come_cpu_edge_cdf,
  * come_cpu_edge_sample and the test-support entry come_cpu_edge_pick (edges sampled by weight for
  * the O1 trainer; come_sgns_o1 is unchanged).
+ * ABI 5, additive: come_topk_scratch, come_row_sqnorms, come_topk and the CPU twin come_cpu_topk
+ * (exact top-k neighbour search over an embedding table).
  * ABI 5, additive: come_walk_cdf, come_random_walks_w and their CPU twins come_cpu_walk_cdf,
  * come_cpu_random_walks_w (edge-weighted walks; the unweighted walkers are unchanged).
  * ABI 5, additive: come_random_walks_pq and its CPU twin come_cpu_random_walks_pq (node2vec
@@ -395,6 +397,36 @@ int come_kmeans_pp_pick(const float *dist, int64_t V, int T, const double *ppot,
 int come_kmeans_pp_sample(const float *closest, int64_t V, const double *cpot, int chunks,
                           int rows_per_chunk, const double *u, int T, int32_t *cand_out,
                           void *stream);
+
+/* ---- Exact top-k neighbour search over an embedding table (come_amd.neighbors) ----
+ * q [Q x d] and base [V x d]: device fp32, row-major.  1 <= k <= 64, 1 <= d <= 512, Q >= 1,
+ * 1 <= V < 2^31.  metric: COME_TOPK_DOT (q.b, larger is better), COME_TOPK_COSINE (q.b / (|q| |b|);
+ * a zero-norm row has inverse norm 0 and scores 0) or COME_TOPK_L2 (max(0, |q|^2 + |b|^2 - 2 q.b),
+ * smaller is better).  idx_out int32 [Q x k] and score_out fp32 [Q x k], best first; equal scores
+ * in ascending base index; a NaN score is never selected; where fewer than k candidates exist the
+ * tail is idx -1, score -inf (+inf for L2).  exclude (optional, device int32 [Q]): the base row
+ * query i must not return, -1 for none.  base_sq (optional, device fp32 [V]): come_row_sqnorms of
+ * base.  No [Q x V] matrix exists and no float atomics run: bit-identical from run to run.
+ *
+ * come_topk_scratch (host): the base chunking for a device with `cus` compute units (<= 0: 256):
+ * chunks_out <= 64 and rows_per_chunk_out, a multiple of the 32-row base tile with chunks *
+ * rows_per_chunk >= V.  The scratch of come_topk (4-byte aligned) is chunks * Q * k * 8 bytes,
+ * plus 4 V bytes when base_sq is NULL.  come_topk accepts any chunks in [1, 64].
+ *
+ * come_row_sqnorms: out[r] = |x_r|^2, an fp32 fmaf chain in feature order.
+ *
+ * come_cpu_topk: the same contract on host arrays with `threads` threads over the queries (fmaf
+ * chains in feature order; on data where the arithmetic is exact, the GPU's bits). */
+enum come_topk_metric { COME_TOPK_DOT = 0, COME_TOPK_COSINE = 1, COME_TOPK_L2 = 2 };
+int come_topk_scratch(int64_t Q, int64_t V, int d, int k, int cus, int *chunks_out,
+                      int64_t *rows_per_chunk_out);
+int come_row_sqnorms(const float *x, int64_t V, int d, float *out, void *stream);
+int come_topk(const float *q, int64_t Q, const float *base, int64_t V, int d, int k, int metric,
+              const int32_t *exclude, const float *base_sq, int chunks, void *scratch,
+              int32_t *idx_out, float *score_out, void *stream);
+int come_cpu_topk(const float *q, int64_t Q, const float *base, int64_t V, int d, int k,
+                  int metric, const int32_t *exclude, const float *base_sq, int32_t *idx_out,
+                  float *score_out, int threads);
 
 /* ---- Random walks: the producer of train_o2's input (utils/graph_utils.py) ----
  * Graphs are CSR over node POSITIONS 0..V-1 in networkx order (see come_graph_from_edges):

@@ -16,6 +16,7 @@ MODE_HOGWILD = 0
 MODE_SEQUENTIAL = 1
 TABLE_PACKED = 0x100  # COME_TABLE_PACKED mode flag
 HOT_NONE = 0x200      # COME_HOT_NONE mode flag
+TOPK_METRICS = {"dot": 0, "cosine": 1, "l2": 2}  # come_topk_metric
 ABI_VERSION = 5       # COME_ABI_VERSION this binding is written for
 
 # Every symbol include/come.h declares (checked by tests/test_capi.py).
@@ -41,7 +42,8 @@ SYMBOLS = ("come_abi_version", "come_last_error", "come_init", "come_exp_table",
            "come_quiet_rows", "come_sgns_o2_quiet", "come_random_walks_pq",
            "come_cpu_random_walks_pq", "come_walk_cdf", "come_cpu_walk_cdf",
            "come_random_walks_w", "come_cpu_random_walks_w", "come_edge_cdf",
-           "come_cpu_edge_cdf", "come_edge_sample", "come_cpu_edge_sample", "come_cpu_edge_pick")
+           "come_cpu_edge_cdf", "come_edge_sample", "come_cpu_edge_sample", "come_cpu_edge_pick",
+           "come_topk_scratch", "come_row_sqnorms", "come_topk", "come_cpu_topk")
 
 OPTION_FIELDS = ("o2_kernel", "o2_blocks_per_cu", "o2_waves_per_block",
                  "o2_static", "rows_per_wave", "o1_rows_per_wave",
@@ -129,6 +131,10 @@ def lib():
     L.come_kmeans_pp_step.argtypes = [P, i64, i32, P, P, i32, i32, P, P, P, P]
     L.come_kmeans_pp_pick.argtypes = [P, i64, i32, P, P, i32, P, P, P, P, P]
     L.come_kmeans_pp_sample.argtypes = [P, i64, P, i32, i32, P, i32, P, P]
+    L.come_topk_scratch.argtypes = [i64, i64, i32, i32, i32, P, P]
+    L.come_row_sqnorms.argtypes = [P, i64, i32, P, P]
+    L.come_topk.argtypes = [P, i64, P, i64, i32, i32, i32, P, P, i32, P, P, P, P]
+    L.come_cpu_topk.argtypes = [P, i64, P, i64, i32, i32, i32, P, P, P, P, i32]
     L.come_make_table.argtypes = [P, i64, P, u64, f64]
     L.come_count_o2_pairs.argtypes = [P, i64, i32, i32]
     L.come_count_o2_pairs.restype = i64

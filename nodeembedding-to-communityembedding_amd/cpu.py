@@ -15,6 +15,7 @@ to them.
     random_walks_w(rowptr, col, wcdf, starts, path_length, alpha, p, q, seed, ...) -> walks[, trials]
     edge_cdf(weights)                                              -> ecdf (edges sampled by weight)
     sample_edges(edges, ecdf, S, seed, offset)                     -> rows[, indices]
+    topk(queries, base, k, metric, exclude, base_sq, threads)      -> (idx, score) (neighbour search)
 
 Tables are updated in place (float32, C-contiguous, as the reference's numpy arrays).  ``mode``:
 MODE_HOGWILD = ``threads`` workers taking jobs of 150 walks / edges with lock-free updates, as the
@@ -347,3 +348,33 @@ def edge_pick(ecdf, r64):
     check(_lib.lib().come_cpu_edge_pick(ptr(ecdf), len(ecdf), ptr(r64), len(r64), ptr(idx)),
           "come_cpu_edge_pick")
     return idx
+
+
+def topk(queries, base, k, metric='cosine', exclude=None, base_sq=None, threads=None):
+    """come_amd.neighbors.topk on host arrays (come_cpu_topk): the k best rows of base [V, d] for
+    every row of queries [Q, d] under 'dot', 'cosine' or 'l2': (idx int64 [Q, k], score fp32
+    [Q, k]), best first, equal scores in ascending index, the tail idx -1 / score -inf (+inf for
+    'l2') where fewer than k candidates exist.  exclude: optional int32 [Q] (-1: none); base_sq:
+    optional fp32 [V] squared base norms."""
+    _arr(queries, np.float32, "queries")
+    _arr(base, np.float32, "base")
+    if queries.ndim != 2 or base.ndim != 2 or queries.shape[1] != base.shape[1]:
+        raise ValueError("queries [Q, d] and base [V, d] must share d")
+    if metric not in _lib.TOPK_METRICS:
+        raise ValueError("metric must be one of %s (got %r)" % (sorted(_lib.TOPK_METRICS), metric))
+    Q, d = queries.shape
+    V = base.shape[0]
+    if exclude is not None:
+        _arr(exclude, np.int32, "exclude")
+        assert exclude.shape == (Q,)
+    if base_sq is not None:
+        _arr(base_sq, np.float32, "base_sq")
+        assert base_sq.shape == (V,)
+    idx = np.empty((Q, int(k)), np.int32)
+    score = np.empty((Q, int(k)), np.float32)
+    check(_lib.lib().come_cpu_topk(ptr(queries), Q, ptr(base), V, d, int(k),
+                                   _lib.TOPK_METRICS[metric],
+                                   None if exclude is None else ptr(exclude),
+                                   None if base_sq is None else ptr(base_sq), ptr(idx), ptr(score),
+                                   _threads(threads)), "come_cpu_topk")
+    return idx.astype(np.int64), score

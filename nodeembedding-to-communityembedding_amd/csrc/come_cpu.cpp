@@ -863,3 +863,109 @@ extern "C" int come_cpu_edge_sample(const int32_t *edges, const uint64_t *ecdf, 
     });
     return COME_OK;
 }
+
+// ---- top-k neighbour search (come_topk's contract on host arrays) ----
+namespace come {
+namespace {
+
+struct Topk {
+    const float *q, *base, *bsq;
+    const int32_t *exclude;
+    int32_t *idx;
+    float *score;
+    int64_t V;
+    int d, k, metric;
+};
+
+// |x|^2 by an fmaf chain in feature order (k_row_sqnorms)
+HOT float row_sqnorm(const float *x, int d) {
+    float s = 0.0f;
+    for (int c = 0; c < d; ++c) s = fmaf(x[c], x[c], s);
+    return s;
+}
+
+inline float inv_norm(float sq) { return sq > 0.0f ? 1.0f / std::sqrt(sq) : (sq == 0.0f ? 0.0f : sq); }
+
+// The kernels' arithmetic per pair: dot by an fmaf chain in feature order, key = fmaf(dot, mul_j,
+// add_j), rank value v = key (dot), key / |q| (cosine), -max(0, |q|^2 - key) (L2); the list holds
+// the k best (v descending, index ascending), kept sorted.  A NaN passes no comparison.
+HOT void topk_rows(const Topk &a, int64_t lo, int64_t hi) {
+    const int d = a.d, k = a.k;
+    std::vector<float> lv(k);
+    std::vector<int32_t> li(k);
+    for (int64_t r = lo; r < hi; ++r) {
+        const float *q = a.q + r * d;
+        const float qsq = a.metric == COME_TOPK_DOT ? 0.0f : row_sqnorm(q, d);
+        const float qf = a.metric == COME_TOPK_COSINE ? inv_norm(qsq) : qsq;
+        const int32_t ex = a.exclude ? a.exclude[r] : -1;
+        int n = 0;
+        for (int64_t j0 = 0; j0 < a.V; j0 += 4) {
+            float dot[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            const float *bp[4];
+            for (int u = 0; u < 4; ++u) bp[u] = a.base + (j0 + u < a.V ? j0 + u : a.V - 1) * d;
+            for (int c = 0; c < d; ++c) {
+                const float qc = q[c];
+                for (int u = 0; u < 4; ++u) dot[u] = fmaf(qc, bp[u][c], dot[u]);
+            }
+            for (int u = 0; u < 4 && j0 + u < a.V; ++u) {
+                const int32_t j = (int32_t)(j0 + u);
+                if (j == ex) continue;
+                float v = dot[u];
+                if (a.metric == COME_TOPK_COSINE) v = fmaf(v, inv_norm(a.bsq[j]), 0.0f) * qf;
+                if (a.metric == COME_TOPK_L2) {
+                    const float d2 = qf - fmaf(v, 2.0f, -a.bsq[j]);
+                    v = -(d2 > 0.0f ? d2 : (d2 <= 0.0f ? 0.0f : d2));
+                }
+                // rows come in ascending index: an equal value loses to every entry held
+                if (n == k && !(v > lv[k - 1])) continue;
+                if (!(v > -INFINITY)) continue;  // NaN, or the score of an empty entry
+                int p = n < k ? n++ : k - 1;
+                for (; p > 0 && v > lv[p - 1]; --p) {
+                    lv[p] = lv[p - 1];
+                    li[p] = li[p - 1];
+                }
+                lv[p] = v;
+                li[p] = j;
+            }
+        }
+        const bool l2 = a.metric == COME_TOPK_L2;
+        for (int e = 0; e < k; ++e) {
+            a.idx[r * k + e] = e < n ? li[e] : -1;
+            a.score[r * k + e] = e < n ? (l2 ? -lv[e] : lv[e]) : (l2 ? INFINITY : -INFINITY);
+        }
+    }
+}
+COME_FMA_CLONE void topk_rows_fma(const Topk &a, int64_t lo, int64_t hi) { topk_rows(a, lo, hi); }
+void topk_rows_base(const Topk &a, int64_t lo, int64_t hi) { topk_rows(a, lo, hi); }
+
+}  // namespace
+}  // namespace come
+
+extern "C" int come_cpu_topk(const float *q, int64_t Q, const float *base, int64_t V, int d, int k,
+                             int metric, const int32_t *exclude, const float *base_sq,
+                             int32_t *idx_out, float *score_out, int threads) {
+    using namespace come;
+    if (Q < 1 || V < 1 || V > INT32_MAX)
+        return set_error(COME_E_INVALID, "cpu_topk: need Q >= 1 and V in [1, 2^31)");
+    if (d < 1 || d > kMaxDim)
+        return set_error(COME_E_INVALID, "cpu_topk: d must be in [1, %d] (got %d)", kMaxDim, d);
+    if (k < 1 || k > 64) return set_error(COME_E_INVALID, "cpu_topk: k must be in [1, 64] (got %d)", k);
+    if (metric != COME_TOPK_DOT && metric != COME_TOPK_COSINE && metric != COME_TOPK_L2)
+        return set_error(COME_E_INVALID, "cpu_topk: unknown metric %d", metric);
+    int rc = check_threads(threads);
+    if (rc) return rc;
+    if (!q || !base || !idx_out || !score_out)
+        return set_error(COME_E_INVALID, "cpu_topk: null pointer");
+    std::vector<float> own;
+    if (!base_sq && metric != COME_TOPK_DOT) {
+        own.resize((size_t)V);
+        parallel_rows(V, threads, [&](int64_t lo, int64_t hi) {
+            for (int64_t r = lo; r < hi; ++r) own[(size_t)r] = row_sqnorm(base + r * d, d);
+        });
+        base_sq = own.data();
+    }
+    const Topk a{q, base, base_sq, exclude, idx_out, score_out, V, d, k, metric};
+    auto fn = have_fma() ? topk_rows_fma : topk_rows_base;
+    parallel_rows(Q, threads, [&](int64_t lo, int64_t hi) { fn(a, lo, hi); });
+    return COME_OK;
+}

@@ -200,6 +200,33 @@ class Model(object):
             return self.table_packed
         return self.table
 
+    # ---- neighbour queries (come_amd.neighbors) ----
+    def most_similar(self, node_ids, topn=10, metric='cosine', table='node'):
+        """The `topn` nodes most similar to each of `node_ids` (the node itself left out):
+        (ids int64 [n, topn], scores fp32 [n, topn]) as numpy arrays, best first.  table: 'node'
+        searches node_embedding, 'context' context_embedding.  Raises KeyError for an id outside
+        the vocabulary.  Where the table has fewer than topn other rows the tail is id -1."""
+        import torch
+        from . import neighbors
+        if table not in ("node", "context"):
+            raise ValueError("table must be 'node' or 'context' (got %r)" % (table,))
+        emb = self.node_embedding if table == "node" else self.context_embedding
+        ids = np.atleast_1d(np.asarray(node_ids, np.int64))
+        rows = self.rows_of(ids)
+        if (rows < 0).any():
+            raise KeyError("node id(s) not in the vocabulary: %s" % ids[rows < 0][:8].tolist())
+        r = torch.from_numpy(rows).to(emb.device)
+        idx, score = neighbors.topk(emb.index_select(0, r), emb, int(topn), metric=metric,
+                                    exclude=r)
+        idx = idx.cpu().numpy()
+        return np.where(idx >= 0, self.node_ids[np.maximum(idx, 0)], -1), score.cpu().numpy()
+
+    def nearest_to_centroids(self, topn=10):
+        """The `topn` rows of node_embedding nearest each community centre (`centroid`), by squared
+        L2 distance: (rows int64 [K, topn], distances fp32 [K, topn]) on the device."""
+        from . import neighbors
+        return neighbors.topk(self.centroid, self.node_embedding, int(topn), metric='l2')
+
     # ---- persistence ----
     def save(self, path='data', file_name=None):
         """torch.save of the model state; numpy arrays are stored as tensors so that

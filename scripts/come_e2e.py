@@ -13,7 +13,9 @@ of the intra- / inter-block edges (the default 1, 1 is the unweighted run); with
 walks are edge-weighted (come_random_walks_w) and the model's counts are the node strengths, from
 which the negative table, the hot rows and the quiet rows are derived.  --weighted-o1 (off by
 default; needs --w-in or --w-out): the O1 passes train edges sampled by weight on the device
-(Node2Vec.train(weights=g.edge_weights)) instead of every edge once.  Prints one JSON line.
+(Node2Vec.train(weights=g.edge_weights)) instead of every edge once.  --knn K: the share of each node's K nearest neighbours (cosine,
+neighbors.knn_graph over the trained node_embedding) that lie in its own block: a record, no bar.
+Prints one JSON line.
 """
 import argparse
 import json
@@ -30,7 +32,7 @@ sys.path.insert(0, ROOT)
 def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negative=5,
         window=5, walk_length=40, num_walks=5, iters=1, lr=0.025, alpha=1.0, beta=0.1,
         com_iters=5, seed=0, reg_covar=1e-5, n_init=3, deterministic=False, log=print, p=1.0,
-        q=1.0, w_in=1.0, w_out=1.0, weighted_o1=False):
+        q=1.0, w_in=1.0, w_out=1.0, weighted_o1=False, knn=0):
     import torch
     from sklearn.metrics import normalized_mutual_info_score
     from come_amd.community_embeddings import Community2Vec
@@ -97,6 +99,15 @@ def run(blocks=100, block_size=1000, p_in=0.016, p_out=4.04e-5, dim=128, negativ
            "o2_pairs": int(pairs), "nmi": nmi,
            "gmm_converged": bool(getattr(cm.g_mixture, "converged_", False)),
            "timings_s": {k: round(v, 4) for k, v in t.items()}}
+    if knn > 0:  # the share of each node's K cosine neighbours that lie in its own block
+        from come_amd.neighbors import knn_graph
+        t0 = time.time()
+        nb, _ = knn_graph(model.node_embedding, knn, metric="cosine")
+        tick("knn_s", t0)
+        nb = nb.cpu().numpy()
+        same = (labels[np.maximum(nb, 0)] == labels[:, None]) & (nb >= 0)
+        out["knn"] = {"k": knn, "same_block_share": float(same.mean()),
+                      "seconds": round(t["knn_s"], 4)}
     if p != 1.0 or q != 1.0:
         out["walk_bias"] = {"p": p, "q": q}
     if weighted:
@@ -124,11 +135,14 @@ def main():
     ap.add_argument("--w-out", type=float, default=1.0, help="weight of the inter-block edges")
     ap.add_argument("--weighted-o1", action="store_true",
                     help="train O1 on edges sampled by weight (needs --w-in or --w-out)")
+    ap.add_argument("--knn", type=int, default=0,
+                    help="also report the share of each node's K nearest neighbours (cosine, "
+                         "neighbors.knn_graph) that lie in its own block (K <= 64)")
     args = ap.parse_args()
     run(blocks=args.blocks, block_size=args.block_size, p_in=args.p_in, p_out=args.p_out,
         dim=args.dim, negative=args.negative, window=args.window, walk_length=args.walk_length,
         num_walks=args.num_walks, iters=args.iters, n_init=args.n_init, p=args.p, q=args.q,
-        w_in=args.w_in, w_out=args.w_out, weighted_o1=args.weighted_o1)
+        w_in=args.w_in, w_out=args.w_out, weighted_o1=args.weighted_o1, knn=args.knn)
 
 
 if __name__ == "__main__":
